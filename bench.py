@@ -25,7 +25,14 @@ lookups instead.  value = (build keys + probe keys) of the whole job / wall
 time of the slowest GPU.  A GPU whose build batch is under 16 M keys (strong
 scaling at N >= 2) runs its build and probe on two streams (--overlap).
 
-    python bench.py [--gpus N --steps K --warmup W] [--rehearse]
+A plain run sets up, warms up, times the K steps and prints the line (value,
+ms_per_step, the sampled pass times and their roofline).  --full adds every
+side measurement and check to the line: the box's streaming ceilings, e2e /
+e2e_hashed, the legacy / block / version_probe / mixed_set / dedup_shifted
+legs and cpu_baseline with its byte-for-byte parity check.  --dump-outputs DIR
+writes the last timed step's filters and masks as DIR/*.npy (dump_outputs).
+
+    python bench.py [--gpus N --steps K --warmup W] [--rehearse] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 """
 from __future__ import annotations
@@ -108,6 +115,15 @@ def main():
                          "(dlsm_multi_device_run), even at N = 1 (the default shape for --gpus N > 1; at N = 1 "
                          "the default is this process's own native-runner loop, or the Python loop when an "
                          "A/B knob or --python-loop needs it)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every side measurement and check: the box's "
+                         "streaming ceilings, the host-inclusive rates, the legacy / block / version / "
+                         "filter-set-shape legs and the CPU baseline with its parity check (each can be "
+                         "dropped again with its --no-* flag); without it the run only sets up, warms up, "
+                         "times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the filters and the probe masks) as "
+                         "DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-e2e", action="store_true")
     ap.add_argument("--no-version", action="store_true",
@@ -400,6 +416,12 @@ def main():
     }
     del rank_keys
 
+    if args.dump_outputs:
+        # the last timed step's outputs, before any --full leg runs the path again
+        L = lens.cpu().numpy()
+        dump_outputs(args.dump_outputs, [outs[s][: int(L[s])].cpu().numpy() for s in range(len(tables))],
+                     mask[: qk.n * fs.mask_bytes].cpu().numpy(), prefix=f"rank{rank}_" if world > 1 else "")
+
     # the committed PMC traffic is for the whole job on one GPU: a rank's
     # share at N > 1 is not what was counted, so it is reported only at N = 1
     traffic = load_traffic(args.traffic, result["config"], dominant) if world == 1 else None
@@ -408,16 +430,20 @@ def main():
         result["roofline"]["traffic_source"] = traffic["source"]
         result["roofline"]["traffic_alg_ratio"] = round(
             traffic["traffic_bytes"] / (probe_bytes if dominant == "probe" else build_bytes), 3)
-    ceil, shapes = stream_ceilings(dev, stream)
-    result["roofline"]["hbm_read_GBs_measured"] = ceil["read"]
-    result["roofline"]["hbm_copy_GBs_measured"] = ceil["copy"]
-    result["roofline"]["frac_of_measured_read"] = round(ach / ceil["read"], 4)
-    result["roofline"]["frac_of_measured_copy"] = round(ach / ceil["copy"], 4)
-    result["roofline"]["ceiling_kernels"] = ("dlsm_stream_kernel, best of plain/nt x grid-stride/chunked x "
-                                             f"1-4K workgroups of 512: {shapes}")
+    # Everything from here to the CPU baseline takes GPU or host runs of its
+    # own beside the timed steps: --full only.
+    full = args.full
+    if full:
+        ceil, shapes = stream_ceilings(dev, stream)
+        result["roofline"]["hbm_read_GBs_measured"] = ceil["read"]
+        result["roofline"]["hbm_copy_GBs_measured"] = ceil["copy"]
+        result["roofline"]["frac_of_measured_read"] = round(ach / ceil["read"], 4)
+        result["roofline"]["frac_of_measured_copy"] = round(ach / ceil["copy"], 4)
+        result["roofline"]["ceiling_kernels"] = ("dlsm_stream_kernel, best of plain/nt x grid-stride/chunked x "
+                                                 f"1-4K workgroups of 512: {shapes}")
 
     # ---- host-inclusive (PCIe) rate, N=1 only: recorded, never `value` ----
-    if world == 1 and not args.no_e2e:
+    if full and world == 1 and not args.no_e2e:
         result["e2e"] = e2e_rate(ctx, stream, tables, outs, lens, fs, qk, mask, bpk, dev)
         L = lens.cpu().numpy()
         ref = ([outs[s][: int(L[s])].cpu().numpy().tobytes() for s in range(len(tables))], mask.cpu().numpy())
@@ -433,7 +459,7 @@ def main():
     # ---- legacy FilterPolicy format over the same tables (config 2's
     # "bit-exact vs util/bloom.cc"), N=1: recorded beside `value` ----
     legacy_out = None
-    if world == 1 and tables and not args.no_legacy:
+    if full and world == 1 and tables and not args.no_legacy:
         result["legacy"], legacy_out = legacy_leg(ctx, stream, tables, bpk)
         lt = load_traffic(args.traffic, result["config"], "legacy") if world == 1 else None
         if lt:  # PMC fabric bytes of one legacy batch build (partition + slice)
@@ -442,7 +468,7 @@ def main():
                 lt["traffic_bytes"] / (result["legacy"]["alg_bytes_per_key"] * len(tables) * tables[0].n), 3)
 
     # ---- the sealed filter block, N=1: recorded ----
-    if world == 1 and tables and not args.no_block:
+    if full and world == 1 and tables and not args.no_block:
         result["block"] = block_leg(ctx, stream, tables, bpk)
         bt = load_traffic(args.traffic, result["config"], "block")
         if bt:  # PMC fabric bytes of one sealed batch build (partition + slice + seal)
@@ -452,7 +478,7 @@ def main():
 
     # ---- the read shapes a Version presents, N=1:
     # recorded beside `value` ----
-    if world == 1 and not args.no_version:
+    if full and world == 1 and not args.no_version:
         result["version_probe"] = version_leg(ctx, stream, dev)
         vt = load_traffic(args.traffic, result["config"], "version")
         if vt:  # fabric bytes (L2 misses, Infinity-Cache hits included) per call
@@ -475,7 +501,7 @@ def main():
             vp["floor_ms"] = round(max(lines_ms, vp["nofilter_ms"]), 4)
             vp["floor_parts_ms"] = {"lines_past_l2_at_ic_rate": round(lines_ms, 4), "nofilter": vp["nofilter_ms"]}
             vp["ms_over_floor"] = round(vp["ms"] / vp["floor_ms"], 3)
-    if world == 1 and not args.no_mixed:
+    if full and world == 1 and not args.no_mixed:
         for name, sizes in SHAPE_LEGS.items():
             rec = shape_leg(ctx, stream, dev, qk, bpk, sizes)
             st = load_traffic(args.traffic, result["config"], name)
@@ -492,7 +518,7 @@ def main():
         dist.all_gather_object(recs, mine)
         result["per_gpu"] = recs
         result["imbalance"] = imbalance(recs)
-    if world == 1 and rank == 0 and not args.no_cpu:
+    if full and world == 1 and rank == 0 and not args.no_cpu:
         filters = [f for f in inp.filters]
         L = lens.cpu().numpy()
         gpu_filters = [outs[s][: int(L[s])].cpu().numpy().tobytes() for s in range(T)]
@@ -556,10 +582,16 @@ def run_threads(args) -> int:
                                         inp.lookups.n * (20 + inp.fs.mask_bytes) + sum(int(f.numel()) for f in inp.filters),
                                         ps, ds, args.steps))
     result = threads_line(args, N_GPU, devices, workers, per_gpu, elapsed, T, N, Q, F, bpk)
-    if not args.no_cpu:
+    order = sorted((s, w, j) for w in workers for j, s in enumerate(w.work.tables))  # table ids are distinct
+    if args.dump_outputs:
+        # the whole job's outputs, as one GPU would have written them
+        dump_outputs(args.dump_outputs,
+                     [w.inp.outs[j][: int(w.inp.lens.cpu().numpy()[j])].cpu().numpy() for _, w, j in order],
+                     np.concatenate([w.inp.mask[: w.work.n_lookups * w.inp.fs.mask_bytes].cpu().numpy()
+                                     for w in workers]))
+    if args.full and not args.no_cpu:
         # the CPU baseline once, from this process, on the job's first tables
         # and GPU 0's lookup shard (bounded sample, as at N = 1)
-        order = sorted((s, w, j) for w in workers for j, s in enumerate(w.work.tables))
         tabs = [w.inp.tables[j] for _, w, j in order]
         gpu_filters = [w.inp.outs[j][: int(w.inp.lens.cpu().numpy()[j])].cpu().numpy().tobytes() for _, w, j in order]
         w0 = workers[0]
@@ -569,6 +601,46 @@ def run_threads(args) -> int:
     for w in workers:
         w.close()
     return 0
+
+
+DUMP_SAMPLE = 4_000_000  # sampled bytes per output (float32: 16 MB each, 32 MB + the sums in all)
+DUMP_CHUNK = 1 << 16     # bytes per chunk sum
+
+
+def dump_outputs(out_dir, filters, mask, prefix=""):
+    """--dump-outputs: what a caller of the timed path holds after its last
+    step -- the SSTables' filters (`filters`: one uint8 array of out_len bytes
+    per table, in table order) and the probe's mask bytes (`mask`: uint8, one
+    byte per lookup per 8 filters) -- as float .npy files under out_dir:
+      filter_lens           float64[T]  each filter's length in bytes
+      filters_sample        float32     bytes of the concatenated filters at
+                                        DUMP_SAMPLE seeded positions (every byte
+                                        when there are no more than that)
+      filters_chunk_sums    float64     sum of every DUMP_CHUNK bytes of the same
+      mask_sample, mask_chunk_sums      the same two views of the mask bytes
+    The sums cover every output byte, the samples compare byte for byte; the
+    positions depend only on the output's length, so two runs with the same
+    arguments write comparable files."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+
+    def views(name, a, seed):
+        a = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
+        if a.size > DUMP_SAMPLE:
+            pos = np.sort(np.random.default_rng(seed).integers(0, a.size, DUMP_SAMPLE))
+            sample = a[pos]
+        else:
+            sample = a
+        padded = np.zeros(-(-a.size // DUMP_CHUNK) * DUMP_CHUNK, dtype=np.uint8)
+        padded[: a.size] = a
+        sums = padded.reshape(-1, DUMP_CHUNK).sum(axis=1, dtype=np.uint64)
+        np.save(os.path.join(out_dir, f"{prefix}{name}_sample.npy"), sample.astype(np.float32))
+        np.save(os.path.join(out_dir, f"{prefix}{name}_chunk_sums.npy"), sums.astype(np.float64))
+
+    np.save(os.path.join(out_dir, prefix + "filter_lens.npy"), np.array([f.size for f in filters], dtype=np.float64))
+    views("filters", np.concatenate(filters) if filters else np.zeros(0, dtype=np.uint8), 1)
+    views("mask", mask, 2)
 
 
 def gpu_share_record(rank, device, build_keys, probe_keys, build_bytes, probe_bytes, passes, device_s, steps):

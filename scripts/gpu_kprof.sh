@@ -16,7 +16,7 @@ for spec in "$@"; do
   mkdir -p "$OUT/$label"
   for e in $envs; do export "$e"; done
   timeout -k 10 180 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$label" -o run -- \
-    python3 bench.py --steps 10 --warmup 2 --no-cpu --no-e2e $args \
+    python3 bench.py --full --steps 10 --warmup 2 --no-cpu --no-e2e $args \
     > "$OUT/$label/bench.json" 2> "$OUT/$label.err" || exit 1
   for e in $envs; do unset "${e%%=*}"; done
 done

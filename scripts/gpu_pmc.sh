@@ -7,7 +7,7 @@ set -o pipefail
 OUT=${1:-gpurun_out/pmc}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-BENCH="python3 bench.py --steps 3 --warmup 1 --no-cpu --no-e2e ${BENCH_ARGS:-}"
+BENCH="python3 bench.py --full --steps 3 --warmup 1 --no-cpu --no-e2e ${BENCH_ARGS:-}"
 timeout -k 10 120 rocprofv3 -L > "$OUT/counters_list.txt" 2>&1 || true
 i=0
 # PMC_GROUPS: ';'-separated counter groups replacing the default ones

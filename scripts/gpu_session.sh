@@ -8,7 +8,7 @@
 # Steps (outputs under OUTDIR, named by the step's index i):
 #   tests [pytest args]         python -m pytest -m gpu (default: tests/)  -> i_pytest.log
 #   smoke                       __graft_entry__.smoke()                   -> i_smoke.log
-#   bench [bench.py args]       one bench line                            -> i_bench.json
+#   bench [bench.py args]       one bench line (--full for its side legs) -> i_bench.json
 #   kprof [bench.py args]       rocprofv3 --kernel-trace --stats of bench  -> i_prof/ + i_kernel_stats.txt
 #   pmc COUNTERS SCRIPT [args]  one rocprofv3 --pmc pass of python3 SCRIPT args (counters
 #                               comma-separated, one word)                 -> pmc/p<i>/

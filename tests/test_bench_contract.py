@@ -93,6 +93,40 @@ def test_threads_line_schema_per_gpu():
     assert line["config"]["gpu_tables"][1] == list(range(1, T, n_gpu))
 
 
+def test_dump_outputs_views(tmp_path, monkeypatch):
+    """--dump-outputs: float .npy files; the chunk sums cover every output
+    byte, the sample is every byte of a small output and DUMP_SAMPLE seeded
+    positions of a larger one, the same from call to call."""
+    import numpy as np
+
+    b = _bench()
+    monkeypatch.setattr(b, "DUMP_SAMPLE", 1000)
+    monkeypatch.setattr(b, "DUMP_CHUNK", 64)
+    rng = np.random.default_rng(5)
+    filters = [rng.integers(0, 256, n, dtype=np.uint8) for n in (300, 901, 64)]
+    mask = rng.integers(0, 256, 777, dtype=np.uint8)
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), filters, mask)
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in
+           ("filter_lens", "filters_sample", "filters_chunk_sums", "mask_sample", "mask_chunk_sums")}
+    for n, a in got.items():
+        assert a.dtype in (np.float32, np.float64), n
+        assert np.array_equal(a, np.load(tmp_path / "b" / (n + ".npy"))), n
+    cat = np.concatenate(filters)
+    assert got["filter_lens"].tolist() == [300, 901, 64]
+    assert got["filters_sample"].shape == (1000,) and set(got["filters_sample"]) <= set(cat.astype(np.float32))
+    assert got["filters_chunk_sums"].shape == (-(-cat.size // 64),) and got["filters_chunk_sums"].sum() == cat.sum()
+    assert got["filters_chunk_sums"][0] == cat[:64].sum()
+    assert got["filters_chunk_sums"][-1] == cat[-(cat.size % 64):].sum()
+    assert np.array_equal(got["mask_sample"], mask.astype(np.float32))  # 777 <= 1000: every byte
+    assert got["mask_chunk_sums"].sum() == mask.sum()
+    # one flipped byte shows in its chunk's sum
+    mask[130] ^= 1
+    b.dump_outputs(str(tmp_path / "c"), filters, mask)
+    diff = np.load(tmp_path / "c" / "mask_chunk_sums.npy") != got["mask_chunk_sums"]
+    assert diff.nonzero()[0].tolist() == [2]
+
+
 def test_e2e_split_balances_cores_and_link():
     """e2e_hashed's split: the host-hashed keys take as long on the host's
     cores as the rest take on the link; tables are hashed before lookups."""

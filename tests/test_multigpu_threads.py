@@ -139,7 +139,7 @@ def test_two_logical_devices_strong_scaling_parity(orc):
 
 @pytest.mark.gpu
 def test_bench_two_gpus_rehearsed():
-    r = _bench(["--gpus", "2", "--rehearse", "--steps", "3", "--warmup", "1", "--keys-per-table", "200000",
+    r = _bench(["--gpus", "2", "--rehearse", "--full", "--steps", "3", "--warmup", "1", "--keys-per-table", "200000",
                 "--lookups", "4000000"], timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -161,7 +161,7 @@ def test_bench_two_gpus_rehearsed():
 def test_bench_one_gpu_native_and_python_loop():
     """N = 1: the default times the steps with the native runner; --python-loop
     the same calls from Python.  Both print a complete bench line."""
-    base = ["--steps", "3", "--warmup", "1", "--keys-per-table", "200000", "--lookups", "4000000",
+    base = ["--full", "--steps", "3", "--warmup", "1", "--keys-per-table", "200000", "--lookups", "4000000",
             "--no-cpu", "--no-e2e"]
     for extra, timed_by in (([], "dlsm_multi_device_run"), (["--python-loop"], "Python loop")):
         r = _bench(base + extra, timeout=600)
@@ -171,6 +171,38 @@ def test_bench_one_gpu_native_and_python_loop():
         assert line["rehearsed"] is False and line["physical_devices"] == 1
         assert line["value"] > 0 and line["probe"]["ms"] > 0 and line["build"]["ms"] > 0
         assert line["roofline"]["hbm_read_GBs_measured"] > 1000
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(orc, tmp_path):
+    """Without --full the line carries the timed steps' figures only (no leg
+    that takes runs of its own), and --dump-outputs writes the last timed
+    step's filters and masks: here small enough that the samples hold every
+    byte, so they are compared with the oracle's byte for byte."""
+    r = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--keys-per-table", str(_N), "--lookups", str(_Q),
+                "--dump-outputs", str(tmp_path / "out")], timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 2 and line["value"] > 0 and line["unit"] == "Mkeys/s" and line["higher_is_better"]
+    assert line["ms_per_step"] > 0 and line["dtype"] == "u32"
+    assert abs(line["value"] - (_T * _N + _Q) / line["ms_per_step"] / 1e3) <= 0.01 * line["value"]
+    assert line["probe"]["ms"] > 0 and line["build"]["ms"] > 0 and line["roofline"]["achieved"] > 0
+    for leg in ("cpu_baseline", "e2e", "e2e_hashed", "other_step_shape", "legacy", "block", "version_probe",
+                "mixed_set", "dedup_shifted"):
+        assert leg not in line, leg
+    assert "hbm_read_GBs_measured" not in line["roofline"]
+    got = {n: np.load(tmp_path / "out" / (n + ".npy")) for n in
+           ("filter_lens", "filters_sample", "filters_chunk_sums", "mask_sample", "mask_chunk_sums")}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    want = [np.frombuffer(orc.full_build(orc.dbbench_keys(s, _T, _N), _N), dtype=np.uint8) for s in range(_T)]
+    assert got["filter_lens"].tolist() == [w.size for w in want]
+    assert np.array_equal(got["filters_sample"], np.concatenate(want).astype(np.float32))
+    assert got["filters_chunk_sums"].sum() == sum(int(w.sum()) for w in want)
+    filters = [orc.full_build(orc.dbbench_keys(f, _F, _N), _N) for f in range(_F)]
+    qk = orc.keys_from_values(orc.mt_values(1000, 2 * _F * _N, _Q))
+    mask = orc.full_probe(filters, qk, _Q, nthreads=8)
+    assert np.array_equal(got["mask_sample"], np.asarray(mask, dtype=np.uint8).astype(np.float32))
+    assert got["mask_chunk_sums"].sum() == int(np.asarray(mask, dtype=np.uint64).sum())
 
 
 @pytest.mark.gpu
