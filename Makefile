@@ -32,8 +32,9 @@ asm: dlsm_amd/csrc/bloom_kernels.hip $(HDR)
 	$(HIPCC) $(HIPFLAGS) --offload-device-only -S $< -o build/asm/bloom_kernels.s \
 	  -Rpass-analysis=kernel-resource-usage 2> build/asm/resource_usage.txt || true
 
-# A/B build with extra defines: make variant TAG=u4 VFLAGS="-DDLSM_PROBE_U=4"
-# -> dlsm_amd/lib/variants/libdlsm_bloom_u4.so (loaded with DLSM_LIB_VARIANT=u4)
+# A/B build: a tagged library from an edited tree, compared with the base in
+# one session: make variant TAG=edit
+# -> dlsm_amd/lib/variants/libdlsm_bloom_edit.so (loaded with DLSM_LIB_VARIANT=edit)
 variant: $(SRC) $(HDR)
 	@mkdir -p build/variants/$(TAG) dlsm_amd/lib/variants
 	for f in $(SRC); do $(HIPCC) $(HIPFLAGS) $(VFLAGS) -c $$f -o build/variants/$(TAG)/$$(basename $$f .hip).o || exit 1; done

@@ -166,7 +166,6 @@ struct dlsm_ctx {
   DevBuf<uint8_t> crc_streams;
   DevBuf<uint32_t> crc_partial;
   DevBuf<uint32_t> crc_tabs;  // fused seal: full_block_crc_tables(crc_tabs_lgr)
-  DevBuf<uint32_t> crc_cnt;   // fused seal: per-job slice counters (zero between calls)
   int crc_tabs_lgr = -1;
   uint64_t crc_tabs_gen = 0;
   DevBuf<uint8_t*> crc_outp;
@@ -323,9 +322,6 @@ bool is_k28(const dlsm_keyset& k) {
 // 8 KiB) while the batch has fewer than two slice workgroups per CU -- a
 // batch of dLSM-sized flush tables (153,846 keys, 3,005 lines) would
 // otherwise leave most CUs idle.  Returns -1 if none fits.
-#ifndef DLSM_BUILD_MIN_LGR
-#define DLSM_BUILD_MIN_LGR 9  // widest-first search starts at 2^9 lines (32 KiB slices)
-#endif
 int choose_build_lgR(const std::vector<uint32_t>& Ls) {
   auto slices = [&](int lg, uint64_t* total) {
     bool ok = true;
@@ -338,13 +334,9 @@ int choose_build_lgR(const std::vector<uint32_t>& Ls) {
     return ok;
   };
   uint64_t total = 0, t2 = 0;
-  // A/B knob: the slice-workgroup count below which the slices narrow
-  // (default two per CU)
-  static const uint64_t min_wgs = [] {
-    const char* e = getenv("DLSM_BUILD_SLICE_MIN_WGS");
-    return e ? strtoull(e, nullptr, 10) : 2ull * kBuildSliceCUs;
-  }();
-  for (int lg = DLSM_BUILD_MIN_LGR; lg <= 11; lg++) {
+  // the slice-workgroup count below which the slices narrow: two per CU
+  constexpr uint64_t min_wgs = 2ull * kBuildSliceCUs;
+  for (int lg = 9; lg <= 11; lg++) {  // widest-first search from 2^9 lines (32 KiB slices)
     if (!slices(lg, &total)) continue;
     while (lg > 7 && total < min_wgs && slices(lg - 1, &t2)) {
       lg--;
@@ -681,7 +673,6 @@ int dlsm_ctx_destroy(dlsm_ctx* ctx) {
   ctx->crc_streams.release();
   ctx->crc_partial.release();
   ctx->crc_tabs.release();
-  ctx->crc_cnt.release();
   ctx->crc_outp.release();
   ctx->crc_cap.release();
   ctx->crc_val.release();
@@ -891,7 +882,7 @@ int dlsm_ctx_stats(dlsm_ctx* ctx, uint64_t* device_allocs, uint64_t* device_byte
   add(ctx->lentries); add(ctx->ltab); add(ctx->pos); add(ctx->smask); add(ctx->hashes);
   add(ctx->vgl); add(ctx->vabyte); add(ctx->vplan);
   add(ctx->st_keys); add(ctx->st_offs); add(ctx->st_out); add(ctx->st_len); add(ctx->st_filter);
-  add(ctx->crc_streams); add(ctx->crc_partial); add(ctx->crc_tabs); add(ctx->crc_cnt); add(ctx->crc_outp); add(ctx->crc_cap);
+  add(ctx->crc_streams); add(ctx->crc_partial); add(ctx->crc_tabs); add(ctx->crc_outp); add(ctx->crc_cap);
   add(ctx->crc_val); add(ctx->sel);
   if (device_allocs) *device_allocs = n;
   if (device_bytes) *device_bytes = b;
@@ -1165,10 +1156,6 @@ int full_build_dev_impl(dlsm_ctx* ctx, const dlsm_build_job* jobs, int n_jobs, i
         ctx->crc_tabs_gen = ctx->crc_tabs.gen;
       }
       crc_part = ctx->crc_partial.p;
-      if (ctx->crc_cnt.cap < static_cast<size_t>(n_jobs) || !ctx->crc_cnt.p) {
-        DLSM_CHECK(ctx->crc_cnt.ensure(n_jobs));
-        DLSM_TRY(hipMemsetAsync(ctx->crc_cnt.p, 0, sizeof(uint32_t) * ctx->crc_cnt.cap, s));  // reset by the sealers after
-      }
     }
     // Job groups of about equal chunk counts: group g's partition (HBM-bound)
     // runs on the helper stream while the context stream runs group g-1's
@@ -1197,7 +1184,7 @@ int full_build_dev_impl(dlsm_ctx* ctx, const dlsm_build_job* jobs, int n_jobs, i
       if (ng > 1) DLSM_CHECK(hand_over(ctx->aux, s, ctx->ev_part[g % kStageEvents]));
       DLSM_TRY(launch_full_slices(ctx->jobs.p, slice0s, n_jobs, s0, slice_at(cut[g + 1]) - s0,
                                   ctx->dchunk.p, ctx->entries.p, ctx->tab.p, lgR, s, crc_part,
-                                  ctx->crc_tabs.p, ctx->crc_cnt.p));
+                                  ctx->crc_tabs.p));
     }
     if (seal) {
       DLSM_TRY(launch_full_block_seal(ctx->jobs.p, n_jobs, crc_part, ctx->crc_tabs.p, lgR, s));
@@ -1641,7 +1628,7 @@ hipError_t mg_layout(dlsm_filterset* fs, hipStream_t s) {
   }
   if (sbase > kMGMaxSlices) return hipSuccess;
   // every group's fixed sub-regions: entries, answers; its table columns
-  const uint32_t C = 1u << mg_chunk_lg(G);
+  constexpr uint32_t C = kMGChunk;
   uint32_t eoff = 0, aoff = 0;
   for (int j = 0; j < G; j++) {
     md[j].tcol = md[j].sbase + static_cast<uint32_t>(j);
@@ -1651,8 +1638,8 @@ hipError_t mg_layout(dlsm_filterset* fs, hipStream_t s) {
     aoff += mg_sub_abytes(C, md[j].S, md[j].lgw);
   }
   if (eoff > 65535u || aoff > 96u * 1024u) return hipSuccess;  // u16 table offsets / the unpermute's LDS
-  // the partition's staging LDS: the largest set of mg_set_size groups
-  const int P = mg_set_size(mg_chunk_lg(G));
+  // the partition's staging LDS: the largest set of kMGSetSize groups
+  constexpr int P = kMGSetSize;
   uint32_t stage = 0;
   for (int j0 = 0; j0 < G; j0 += P) {
     uint32_t st = 0;
@@ -1864,13 +1851,8 @@ namespace {
 // so the slices are narrowed to R = ceil(L / floor(256 / parts)) lines to fill
 // the 256 CUs exactly -- 8 x 1.6 M-key filters (31,251 lines): 128 slices of
 // 245 lines x 2 parts = 256 workgroups instead of 123 x 2 = 246.
-// ($DLSM_PROBE_BALANCE=0: full-width slices, for A/B.)  Returns S, or 0
-// when the group cannot be sliced.
+// Returns S, or 0 when the group cannot be sliced.
 uint32_t group_slices(const dlsm_ctx* ctx, const ProbeGroup& g, int* lgR, uint32_t* R_out) {
-  static const bool balance = [] {
-    const char* e = getenv("DLSM_PROBE_BALANCE");
-    return !(e && atoi(e) == 0);
-  }();
   const uint32_t L = g.L;
   if (g.lgw < 3) {
     *lgR = 11 - g.lgw;
@@ -1884,7 +1866,7 @@ uint32_t group_slices(const dlsm_ctx* ctx, const ProbeGroup& g, int* lgR, uint32
   uint32_t R = Rmax;
   const uint32_t per_cu = *lgR == 7 && g.lgw == 3 ? 2u : 1u;  // slice workgroups resident per CU
   const uint32_t slots = kBuildSliceCUs * per_cu;
-  if (balance && S0 < slots) {
+  if (S0 < slots) {
     const uint32_t parts = std::max(1u, slots / S0);
     const uint32_t S_target = slots / parts;
     R = std::min(Rmax, ceil_div_u32(L, S_target));
@@ -1896,19 +1878,9 @@ uint32_t group_slices(const dlsm_ctx* ctx, const ProbeGroup& g, int* lgR, uint32
 // (slice, part) workgroups of the slice pass: about one resident wave of
 // workgroups (256 CUs x 2 slices of 64 KiB or 1 of 128 KiB), each part at
 // least one chunk per wave (a part's waves split its chunks into equal
-// groups).  ($DLSM_SLICE_WGS_PER_CU overrides the 2 / 1 slices per CU,
-// $DLSM_SLICE_PARTS the parts: A/B knobs.)
+// groups).
 int slice_parts(uint32_t S, uint32_t nC, int lgR) {
-  static const uint32_t per_cu_env = [] {
-    const char* e = getenv("DLSM_SLICE_WGS_PER_CU");
-    return e ? static_cast<uint32_t>(atoi(e)) : 0u;
-  }();
-  static const int parts_env = [] {  // A/B knob: parts per slice
-    const char* e = getenv("DLSM_SLICE_PARTS");
-    return e ? atoi(e) : 0;
-  }();
-  if (parts_env > 0) return parts_env;
-  const uint32_t resident = 256u * (per_cu_env ? per_cu_env : (lgR == 7 ? 2u : 1u));
+  const uint32_t resident = 256u * (lgR == 7 ? 2u : 1u);
   int parts = static_cast<int>(std::max<uint32_t>(1, (resident + S / 2) / S));
   return std::min<int>(parts, static_cast<int>(std::max<uint32_t>(1, nC / 16)));
 }
@@ -1978,8 +1950,8 @@ int probe_multi(dlsm_ctx* ctx, const dlsm_filterset* fs, const KeyDesc& kd, int 
   hipStream_t s = ctx->stream;
   const uint64_t n = kd.n;
   const int G = fs->mg_n;
-  const int lgC = mg_chunk_lg(G);
-  const uint64_t C = 1ull << lgC;
+  constexpr int lgC = kMGChunkLg;
+  constexpr uint64_t C = kMGChunk;
   const uint32_t rowlen = fs->mg_slices + static_cast<uint32_t>(G);
   const uint64_t mbytes = (fs->F + 7) / 8;
   // Rounds of probe_round keys (DLSM_OPT_PROBE_ROUND_KEYS), pipelined over
@@ -2059,8 +2031,7 @@ int full_probe_dev_impl(dlsm_ctx* ctx, const dlsm_filterset* fs, const dlsm_keys
     DLSM_TRY(launch_probe_direct(fs->d_filters, fs->F, kd, mask_dev, mode, s));
     return DLSM_OK;
   }
-  if (fs->mg_n > 0 && ctx->probe_multi && fs->groups.size() > 1 &&
-      keys->n <= (0xffffffffull << mg_chunk_lg(fs->mg_n)))
+  if (fs->mg_n > 0 && ctx->probe_multi && fs->groups.size() > 1 && keys->n <= (0xffffffffull << kMGChunkLg))
     return probe_multi(ctx, fs, kd, mode, mask_dev);
   if (fs->groups.size() > 1 || !all_sliceable) return probe_grouped(ctx, fs, kd, mode, mask_dev);
 

@@ -143,14 +143,8 @@ struct LegacyTileJobDev {
   int32_t reserved;
 };
 constexpr uint32_t kLegacyTileLg = 16;  // bits per tile: 2^16 (8 KiB of LDS)
-#ifndef DLSM_LEGACY_CHUNK
-#define DLSM_LEGACY_CHUNK 4096  // keys per legacy partition chunk
-#endif
-#ifndef DLSM_LEGACY_NT
-#define DLSM_LEGACY_NT 512      // threads per legacy partition workgroup
-#endif
-constexpr int kLegacyChunk = DLSM_LEGACY_CHUNK;
-constexpr int kLegacyPartBlock = DLSM_LEGACY_NT;
+constexpr int kLegacyChunk = 4096;      // keys per legacy partition chunk
+constexpr int kLegacyPartBlock = 512;   // threads per legacy partition workgroup
 // Partition variants (static LDS staging of one chunk region of u16 entries:
 // k positions per key + up to 7 pads per tile): A: k <= 6, <= 512 tiles;
 // B: k <= 8, <= 4 x threads - 1 tiles (the bins one block scan covers: 1,023
@@ -168,10 +162,7 @@ constexpr int kLegacySliceBlock = 1024;
 constexpr int kBlock = 256;
 constexpr int kMaxSlices = 256;     // slice bins per table in one partition pass
 constexpr uint32_t kBuildSliceCUs = 256;  // MI355X CUs: the build's slice-count target (choose_build_lgR)
-#ifndef DLSM_BUILD_CHUNK
-#define DLSM_BUILD_CHUNK 4096
-#endif
-constexpr int kBuildChunk = DLSM_BUILD_CHUNK;  // keys per partition chunk (build)
+constexpr int kBuildChunk = 4096;  // keys per partition chunk (build)
 // The build partition pads every slice bucket of a chunk to whole 16-byte
 // units (pad entries have bit 31 set), so the slice pass loads 4 entries per
 // lane per load; each chunk owns a region of kBuildRegion entries (its keys
@@ -205,8 +196,7 @@ hipError_t launch_full_partition(const FullJobDev* jobs, const uint32_t* chunk0s
 hipError_t launch_full_slices(const FullJobDev* jobs, const uint32_t* slice0s, int n_jobs,
                               uint32_t slice_first, uint32_t n_slices, const uint32_t* dchunk,
                               const uint32_t* entries, const uint16_t* tab, int lgR, hipStream_t s,
-                              uint32_t* crc_part = nullptr, const uint32_t* crc_tabs = nullptr,
-                              uint32_t* crc_cnt = nullptr);  // per-job counters, zero between calls
+                              uint32_t* crc_part = nullptr, const uint32_t* crc_tabs = nullptr);
 // Seal each job's filter as a filter block (after its sliced build with
 // crc_part): [filter][type 0][masked crc32c], out_len += 5.
 hipError_t launch_full_block_seal(const FullJobDev* jobs, int n_jobs, const uint32_t* crc_part,
@@ -294,12 +284,13 @@ struct MGroupDev {
 constexpr int kMGMaxGroups = 16;
 constexpr uint32_t kMGMaxSlices = 1024;
 constexpr uint32_t kMGPad = 8;  // entries per bucket padding unit (two 16-byte units: whole answer bytes at W = 1)
-// Keys per chunk of the one-pass partition (u16 table offsets into the chunk
-// region of G * C entries + padding), so larger sets take smaller chunks.
-#ifndef DLSM_MG_LG8
-#define DLSM_MG_LG8 11  // chunk lg for sets of <= 8 groups (A/B knob; 12: 4,096-key chunks)
-#endif
-constexpr int mg_chunk_lg(int G) { return G <= 8 ? DLSM_MG_LG8 : 11; }
+// The one-pass partition's one shape: 2,048-key chunks (u16 table offsets into
+// the chunk region of G * C entries + padding), 256 threads, the groups
+// bucketed two per phase (DESIGN.md "Settled experiments").
+constexpr int kMGChunkLg = 11;
+constexpr int kMGChunk = 1 << kMGChunkLg;
+constexpr int kMGSetSize = 2;
+constexpr int kMGPartBlock = 256;
 // Entries of group j's sub-region and bytes of its answer sub-area.
 constexpr uint32_t mg_sub_entries(uint32_t C, uint32_t S) { return C + kMGPad * S; }
 constexpr uint32_t mg_sub_abytes(uint32_t C, uint32_t S, int lgw) {
@@ -310,10 +301,6 @@ constexpr uint32_t mg_sub_abytes(uint32_t C, uint32_t S, int lgw) {
 hipError_t launch_probe_mpartition(KeyDesc keys, const MGroupDev* groups, int G, uint32_t rowlen,
                                    uint32_t region, uint32_t stage_bytes, uint32_t* entries, uint16_t* pos,
                                    uint16_t* tab, int mode, hipStream_t s);
-#ifndef DLSM_MG_P
-#define DLSM_MG_P 2     // groups bucketed per phase of the partition (2,048-key chunks)
-#endif
-constexpr int mg_set_size(int lgC) { return lgC == 11 ? DLSM_MG_P : 2; }
 // The slices [s0, s0 + S) of one image-width class (every group with image
 // width lgw; K: 6 when every such group has k = 6, else 0 = the group's k),
 // workgroups per slice from plan (S + 1 starts, wgs = plan[S]).

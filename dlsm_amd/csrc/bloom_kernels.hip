@@ -281,9 +281,6 @@ __device__ __forceinline__ uint32_t hash_k20_lds(const uint32_t* w) {
 
 // Hash keys [first, first+nk) of kd into h[PER] (key r*NT+t -> thread t, h[r]).
 // `tile` is LDS scratch of K20Tile<NT, KPT>::kVec uint4 (K20 only).
-#ifndef DLSM_TILE_ALL
-#define DLSM_TILE_ALL 1  // hash_chunk: all key tiles of a chunk loaded at once (when they fit 16 uint4)
-#endif
 constexpr int kTileKPT = 2;  // keys per thread per LDS tile (20 KiB tiles at 512 threads)
 // K28 (28-byte internal keys, ExtractUserKey = the first 20 bytes): the same
 // LDS tiles at stride 7 dwords (odd: conflict-free), one key per thread per
@@ -338,7 +335,7 @@ __device__ __forceinline__ void hash_chunk(const KeyDesc& kd, uint64_t first, ui
     constexpr int NTILES = PER / KPT;
     const uint8_t* base = kd.bytes + first * KB;
     const uint32_t nbytes = nk * KB;
-    if constexpr (DLSM_TILE_ALL && NTILES * TL::kPer <= 16) {
+    if constexpr (NTILES * TL::kPer <= 16) {
       // every tile's loads in flight at once (one HBM round trip per chunk,
       // not one per tile: short, non-persistent grids are latency-bound)
       uint4 all[NTILES][TL::kPer];
@@ -676,9 +673,8 @@ struct SegWalk {
   }
 };
 
-// Window sets in flight per wave: set i+DEPTH's loads are issued before set i
-// is consumed.  DEPTH 2 keeps two sets of loads in flight (the walk of a
-// U = 1 unit window is short next to a loaded HBM round trip).
+// One window set of loads in flight per wave: set i+1's loads are issued
+// before set i is consumed.
 template <int U, uint32_t CHUNK, typename E>
 struct WinSet {
   uint32_t idx[U], g;
@@ -694,13 +690,12 @@ struct NoPrologue {
 // run by every wave after the first row loads are issued and before they are
 // used -- their round trip overlaps it.  Every wave runs it, walk or not, so
 // it may hold workgroup barriers.
-template <int U, uint32_t CHUNK, typename E = uint32_t, int DEPTH = 1, bool NTL = false, typename Act,
+template <int U, uint32_t CHUNK, typename E = uint32_t, bool NTL = false, typename Act,
           typename Pro = NoPrologue>
 __device__ __forceinline__ void walk_segments(const uint16_t* tb, uint32_t rowlen, const uint32_t* entries,
                                               uint32_t g_first, uint32_t g_step, uint32_t g_end, uint32_t gs,
                                               uint32_t* scratch, Act act, Pro pro = Pro{},
                                               uint32_t chunk_rt = 0) {
-  static_assert(DEPTH == 1 || DEPTH == 2, "walk depth");
   SegWalk<U, CHUNK, E, NTL> w{tb, entries, rowlen, g_step, g_end, gs};
   w.chunk_rt = chunk_rt;
   w.scr = (lds_u32*)scratch;  // generic -> LDS address space (addrspacecast)
@@ -709,7 +704,7 @@ __device__ __forceinline__ void walk_segments(const uint16_t* tb, uint32_t rowle
   pro();
   if (!any) return;
   w.setup(row0);
-  WinSet<U, CHUNK, E> A, B;
+  WinSet<U, CHUNK, E> A;
   if (!w.next(A.idx, A.ok, A.g)) return;
   w.fetch(A.idx, A.g, A.hv);
   // The first set's loads land in A's registers, which the loop refills by
@@ -718,25 +713,13 @@ __device__ __forceinline__ void walk_segments(const uint16_t* tb, uint32_t rowle
   // iteration's prefetch -- each set's loads were waited on where they were
   // issued.  Waiting once here keeps the loop's waits at the copies.
   __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
-  bool haveB = false;
-  if constexpr (DEPTH == 2) {
-    haveB = w.next(B.idx, B.ok, B.g);
-    if (haveB) w.fetch(B.idx, B.g, B.hv);
-  }
   while (true) {
     WinSet<U, CHUNK, E> N;
-    const bool more = (DEPTH == 1 || haveB) && w.next(N.idx, N.ok, N.g);
+    const bool more = w.next(N.idx, N.ok, N.g);
     if (more) w.fetch(N.idx, N.g, N.hv);
     act(A.hv, A.idx, A.ok, A.g);
-    if constexpr (DEPTH == 1) {
-      if (!more) break;
-      A = N;
-    } else {
-      if (!haveB) break;
-      A = B;
-      B = N;
-      haveB = more;
-    }
+    if (!more) break;
+    A = N;
   }
 }
 
@@ -933,21 +916,14 @@ __device__ __forceinline__ uint32_t crc_mulmod(uint32_t a, uint32_t b) {
   }
   return p;
 }
-#ifndef DLSM_CRC_NIB
-#define DLSM_CRC_NIB 1  // slice CRC by 4-bit tables (8 conflict-free lookups / word) instead of byte tables
-#endif
+// T: 8 tables of 16 (nibble q of the register): 16 entries in 16 banks, so a
+// lookup instruction never conflicts (random byte tables: ~3.5-way).
 __device__ __forceinline__ uint32_t crc_word(uint32_t r, uint32_t w, const uint32_t* T) {
   r ^= w;
-  if constexpr (DLSM_CRC_NIB) {
-    // T: 8 tables of 16 (nibble q of the register): 16 entries in 16 banks,
-    // so a lookup instruction never conflicts (random byte tables: ~3.5-way)
-    uint32_t x = 0;
+  uint32_t x = 0;
 #pragma unroll
-    for (int q = 0; q < 8; q++) x ^= T[16 * q + ((r >> (4 * q)) & 15u)];
-    return x;
-  } else {
-    return T[768 + (r & 0xffu)] ^ T[512 + ((r >> 8) & 0xffu)] ^ T[256 + ((r >> 16) & 0xffu)] ^ T[r >> 24];
-  }
+  for (int q = 0; q < 8; q++) x ^= T[16 * q + ((r >> (4 * q)) & 15u)];
+  return x;
 }
 template <uint32_t R>
 __device__ __forceinline__ uint32_t crc_slice_partial(const uint32_t* sl, uint32_t nl, bool seed,
@@ -980,36 +956,6 @@ __device__ __forceinline__ uint32_t crc_slice_partial(const uint32_t* sl, uint32
   return t;
 }
 
-#ifndef DLSM_SEAL_LAST
-#define DLSM_SEAL_LAST 0  // 1: the last slice workgroup of a job seals it (0: a seal kernel launch)
-#endif
-// The crc32c register after a filter's L lines from its slices' partials
-// (slice s's register times x^(8 * bytes of the slices after it): P1 for
-// whole slices, P64 for the last slice's lines); the workgroup's threads fold
-// a slice each.  Partials are read with agent-scope loads (other XCDs wrote
-// them).  The result is meaningful in thread 0.
-template <uint32_t R>
-__device__ __forceinline__ uint32_t crc_seal_fold(const uint32_t* part, uint32_t L, const uint32_t* crc_tabs,
-                                                  uint32_t* wsum) {
-  const uint32_t S = (L + R - 1u) / R;  // slices holding bytes
-  const uint32_t* P1 = crc_tabs + 1024 + kSliceBlock;
-  const uint32_t* P64 = P1 + 256;
-  uint32_t x = 0;
-  for (uint32_t t = threadIdx.x; t + 1u < S; t += kSliceBlock)
-    x ^= crc_mulmod(__hip_atomic_load(part + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), P1[S - 2u - t]);
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) x ^= __shfl_xor(x, d, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = x;
-  __syncthreads();
-  if (threadIdx.x != 0) return 0;
-  x = 0;
-#pragma unroll
-  for (int w = 0; w < kSliceBlock / 64; w++) x ^= wsum[w];
-  if (S == 0) return 0xffffffffu;  // no lines: the trailer's first byte starts the crc
-  return crc_mulmod(x, P64[L - (S - 1u) * R]) ^
-         __hip_atomic_load(part + (S - 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 // Run the register through the trailer (k, Fixed32 L) and the type byte (0);
 // append [type 0][crc32c::Mask(value)] at `t` (table/table_builder_computeside.cc:418-428).
 __device__ __forceinline__ void crc_seal_append(uint8_t* t, uint32_t r, uint32_t L, int k) {
@@ -1030,50 +976,15 @@ __device__ __forceinline__ void crc_seal_append(uint8_t* t, uint32_t r, uint32_t
   t[2] = static_cast<uint8_t>(m >> 8);
   t[3] = static_cast<uint8_t>(m >> 16);
   t[4] = static_cast<uint8_t>(m >> 24);
-}        // build slices (32 KiB LDS -> 4 per CU)
-// probe slices: 64 KiB LDS per workgroup, 512 or 1024 threads (launch_probe_slices)
-#ifndef DLSM_BUILD_WALKU
-#define DLSM_BUILD_WALKU 8
-#endif
-#ifndef DLSM_BUILD_DEPTH
-#define DLSM_BUILD_DEPTH 1  // window sets of entry loads in flight per wave (build walk)
-#endif
-#ifndef DLSM_BUILD_GS
-#define DLSM_BUILD_GS 0     // chunks per wave group for jobs of >= 256 chunks (0: 64)
-#endif
-constexpr int kWalkU = DLSM_BUILD_WALKU;  // hashes in flight per lane (build segment walk)
-#ifndef DLSM_PROBE_U
-#define DLSM_PROBE_U 1
-#endif
-#ifndef DLSM_PROBE_NTL
-#define DLSM_PROBE_NTL 1  // non-temporal entry loads in the probe slice pass
-#endif
-#ifndef DLSM_PROBE_DEPTH
-#define DLSM_PROBE_DEPTH 1  // window sets of loads in flight per wave (walk_segments)
-#endif
-#ifndef DLSM_PROBE_NT
-#define DLSM_PROBE_NT 1024  // probe slice workgroup size (two 64 KiB slices per CU)
-#endif
-#ifndef DLSM_PROBE_MINWAVES
-#define DLSM_PROBE_MINWAVES 1
-#endif
-#ifndef DLSM_PROBE_U8
-#define DLSM_PROBE_U8 2
-#endif
-constexpr int kProbeWalkU = DLSM_PROBE_U;    // probe walk, 64 KiB slices: unit windows in flight per wave
-constexpr int kProbeWalkU8 = DLSM_PROBE_U8;  // probe walk, 128 KiB slices
-
-// Publish a slice's crc partial at agent scope and count the slice in its
-// job's counter (thread 0); *last = 1 in the workgroup whose count completes
-// the job.  The caller's next barrier makes *last visible.
-[[maybe_unused]] __device__ __forceinline__ void publish_slice_crc(uint32_t* part_slot, uint32_t part, uint32_t* cnt,
-                                                  uint32_t n_slices, uint32_t* last) {
-  if (threadIdx.x == 0) {
-    __hip_atomic_store(part_slot, part, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __threadfence();
-    *last = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == n_slices ? 1u : 0u;
-  }
 }
+
+// Walk widths, measured per pass (DESIGN.md "Settled experiments"):
+// build slices hold 32 KiB of LDS (4 workgroups per CU), probe slices 64 or
+// 128 KiB at kProbeSliceBlock threads (two 64 KiB slices per CU).
+constexpr int kWalkU = 8;        // hashes in flight per lane (build segment walk)
+constexpr int kProbeWalkU = 1;   // probe walk, 64 KiB slices: unit windows in flight per wave
+constexpr int kProbeWalkU8 = 2;  // probe walk, 128 KiB slices
+constexpr int kProbeSliceBlock = 1024;  // probe slice workgroup size
 
 // CRC: the sealed filter block: once its lines
 // are in LDS, the slice also computes the crc32c register contribution of its
@@ -1081,24 +992,22 @@ constexpr int kProbeWalkU8 = DLSM_PROBE_U8;  // probe walk, 128 KiB slices
 // a filter's partials, runs them through the trailer and the type byte, and
 // appends [type 0][masked crc] -- no second pass over the filter bytes.
 // Measured (profiles/r06_block_seal_ab.txt): the slice pass 50 -> 65-69 us
-// for the bench's 16 x 2 MB filters plus a 5 us seal launch; sealing in the
-// last slice workgroup of each filter instead (DLSM_SEAL_LAST=1: agent-scope
-// partials, a release fence and a counter) costs more, 85-93 us, the fences.
+// for the bench's 16 x 2 MB filters plus a 5 us seal launch (sealing in each
+// filter's last slice workgroup instead: 85-93 us, so the seal stays a launch).
 template <int LGR, bool CRC = false>
 __global__ __launch_bounds__(kSliceBlock) void full_slice_kernel(
     const FullJobDev* __restrict__ jobs, const uint32_t* __restrict__ slice0s, int n_jobs,
     const uint32_t* __restrict__ dchunk, const uint32_t* __restrict__ entries,
     const uint16_t* __restrict__ tab, uint32_t block0, uint32_t* __restrict__ crc_part = nullptr,
-    const uint32_t* __restrict__ crc_tabs = nullptr, uint32_t* __restrict__ crc_cnt = nullptr) {
+    const uint32_t* __restrict__ crc_tabs = nullptr) {
   constexpr uint32_t R = 1u << LGR;
   constexpr int NW = kSliceBlock / 64;
   __shared__ __attribute__((aligned(16))) uint32_t sl[R * 16];
   __shared__ uint32_t wsum[NW];
   __shared__ uint32_t walk_scr[NW * kWalkScratch];
   // crc32c tables (nibble: 512 B; 4 KiB more LDS would cost a workgroup per CU)
-  __shared__ uint32_t crcT[CRC ? (DLSM_CRC_NIB ? 128 : 1024) : 1];
+  __shared__ uint32_t crcT[CRC ? 128 : 1];
   __shared__ int sj;
-  __shared__ uint32_t s_last;  // CRC: this workgroup completed its job's slice count
   const int tid = threadIdx.x;
   const int wv = wave_id();  // wave-uniform (SGPR): keeps the segment walk's control flow scalar
   const uint32_t bid = xcd_block(blockIdx.x, gridDim.x) + block0;  // slice index over all jobs
@@ -1110,15 +1019,11 @@ __global__ __launch_bounds__(kSliceBlock) void full_slice_kernel(
   if constexpr (CRC) crc_shift = crc_tabs[1024 + kSliceBlock - 1 - tid];
   for (uint32_t w = tid; w < R * 16; w += kSliceBlock) sl[w] = 0;
   if constexpr (CRC) {
-    if constexpr (DLSM_CRC_NIB) {
-      // nibble table q (byte q / 2 of the register, low or high half) from
-      // the byte table the slice-by-4 step uses for that byte (linear in it)
-      if (tid < 128u) {
-        const uint32_t q = tid >> 4, v = tid & 15u;
-        crcT[tid] = crc_tabs[(3u - (q >> 1)) * 256u + (v << (4u * (q & 1u)))];
-      }
-    } else {
-      for (uint32_t w = tid; w < 1024u; w += kSliceBlock) crcT[w] = crc_tabs[w];
+    // nibble table q (byte q / 2 of the register, low or high half) from
+    // the byte table the slice-by-4 step uses for that byte (linear in it)
+    if (tid < 128u) {
+      const uint32_t q = tid >> 4, v = tid & 15u;
+      crcT[tid] = crc_tabs[(3u - (q >> 1)) * 256u + (v << (4u * (q & 1u)))];
     }
     asm volatile("" : "+v"(crc_shift));
   }
@@ -1145,12 +1050,10 @@ __global__ __launch_bounds__(kSliceBlock) void full_slice_kernel(
       // chunks per wave group: every wave gets a share of a small job's chunks
       // (a job of >= 256 chunks keeps whole 64-chunk groups: measured 2 %
       // faster at 391 chunks than 8 groups of 49, gpurun_out v19b)
-      const uint32_t gs = nC >= 256u ? (DLSM_BUILD_GS ? min(64u, max(1u, (nC + NW - 1) / NW))
-                                                        : 64u)
-                                     : max(1u, (nC + NW - 1) / NW);
+      const uint32_t gs = nC >= 256u ? 64u : max(1u, (nC + NW - 1) / NW);
       // 16-byte units of 4 entries per lane per load (padding entries skipped)
       constexpr int U4 = kWalkU / 4;
-      walk_segments<U4, kBuildRegion / 4, uint4, DLSM_BUILD_DEPTH>(
+      walk_segments<U4, kBuildRegion / 4, uint4>(
           tb, J.n_slices + 1, ent, wv * gs, NW * gs, nC, gs, walk_scr + wv * kWalkScratch,
           [&](const uint4 (&hv)[U4], const uint32_t (&)[U4], const bool (&ok)[U4], uint32_t) {
             if (k == 6) {  // bits_per_key 10 (ChooseNumProbes): straight-line probes
@@ -1183,42 +1086,13 @@ __global__ __launch_bounds__(kSliceBlock) void full_slice_kernel(
     }
     __syncthreads();
     const uint32_t nl = min(R, L - lo_line);
-    // CRC + DLSM_SEAL_LAST: the partial is published before the filter
-    // stores, so that the release fence does not wait for them to drain
-    constexpr bool early = CRC && DLSM_SEAL_LAST;
-    if constexpr (early) part = crc_slice_partial<R>(sl, nl, s == 0, crcT, crc_shift, wsum);
-    if constexpr (early) publish_slice_crc(crc_part + bid, part, crc_cnt + sj, J.n_slices, &s_last);
     uint4* dst = reinterpret_cast<uint4*>(J.out + static_cast<uint64_t>(lo_line) * 64u);
     const uint4* src = reinterpret_cast<const uint4*>(sl);
     for (uint32_t w = tid; w < nl * 4u; w += kSliceBlock) st_global16(dst + w, src[w]);
-    if constexpr (CRC && !early) part = crc_slice_partial<R>(sl, nl, s == 0, crcT, crc_shift, wsum);
-  } else if constexpr (CRC && DLSM_SEAL_LAST) {
-    publish_slice_crc(crc_part + bid, 0u, crc_cnt + sj, J.n_slices, &s_last);  // no bytes past a lowered L
+    if constexpr (CRC) part = crc_slice_partial<R>(sl, nl, s == 0, crcT, crc_shift, wsum);
   }
   if constexpr (CRC) {
-#if DLSM_SEAL_LAST
-    // The job's last slice workgroup to finish seals the filter (no seal
-    // launch): every slice publishes its partial at agent scope, then counts
-    // itself in the job's counter (publish_slice_crc, before its filter
-    // stores); the one that completes the count reads the partials back
-    // (agent-scope loads after an acquire fence), writes the trailer, the
-    // block trailer and the length, and resets the counter for the next call.
-    // Only the sealer writes the trailer bytes and out_len.
-    __syncthreads();
-    if (s_last) {
-      __threadfence();
-      const uint32_t r = crc_seal_fold<R>(crc_part + J.slice0, L, crc_tabs, wsum);
-      if (tid == 0) {
-        write_trailer(J.out, L, J.k);
-        crc_seal_append(J.out + len, r, L, J.k);
-        *J.out_len = len + 5u;
-        crc_cnt[sj] = 0;
-      }
-    }
-    return;
-#else
     if (tid == 0) crc_part[bid] = part;
-#endif
   }
   if (s == 0 && tid == 0) {
     write_trailer(J.out, L, J.k);
@@ -1450,12 +1324,11 @@ __device__ __forceinline__ void for_buckets(uint32_t n, F f) {
 // grouped by slice, every bucket padded to a multiple of 4 entries with
 // kProbePadEntry, so the slice pass moves whole 16-byte units; pos[i] = where
 // key i went.  NT threads per chunk of C keys (C/NT keys per thread).
-// NTS: non-temporal stores of the intermediates (default); plain stores
-// leave them in the Infinity Cache for a round-sized batch to re-read.
+// The intermediates go out with non-temporal stores (store16).
 // PERSIST: a grid smaller than the chunk count loops over the chunks with
 // the next chunk's key tiles in flight; otherwise one workgroup per chunk
 // (the default: no cross-chunk state to keep in registers).
-template <int MODE, int NT, int C, int H = 1, bool NTS = true, bool PERSIST = true>
+template <int MODE, int NT, int C, int H = 1, bool PERSIST = true>
 __global__ __launch_bounds__(NT, (NT <= 512 && H > 1) ? 4 : 1) void probe_partition_kernel(
     KeyDesc kd, uint32_t L, uint32_t magic, uint32_t R, uint32_t rmagic, uint32_t S, uint32_t nC,
     uint32_t* __restrict__ entries, uint16_t* __restrict__ pos, uint16_t* __restrict__ tab) {
@@ -1586,8 +1459,8 @@ __global__ __launch_bounds__(NT, (NT <= 512 && H > 1) ? 4 : 1) void probe_partit
     // every wait is a full vmcnt(0) that would also wait for their acks.
     if constexpr (kPipe) __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
     // coalesced 16-byte stores of the bucketed entries and of the positions
-    store_chunk_u32<NT, NTS>(entries + static_cast<uint64_t>(c) * CR, stage, total);
-    store_chunk_u16<NT, NTS>(pos + first, rk, nk);
+    store_chunk_u32<NT, true>(entries + static_cast<uint64_t>(c) * CR, stage, total);
+    store_chunk_u16<NT, true>(pos + first, rk, nk);
     __syncthreads();  // LDS reused by the next chunk
   }
 }
@@ -1637,7 +1510,7 @@ __device__ __forceinline__ uint32_t packed_answer(uint32_t acc, uint32_t slotmap
 // the arguments; table rows hold `rowlen` offsets and chunk regions `cre_rt`
 // entries (both known at run time only).
 template <int LGR, int LGW, int K, int NT, int C, uint32_t CRE = probe_region(C), bool MG = false>
-__global__ __launch_bounds__(NT, DLSM_PROBE_MINWAVES) void probe_slice_kernel(
+__global__ __launch_bounds__(NT) void probe_slice_kernel(
     const uint8_t* __restrict__ stacked, uint32_t L, uint32_t Rs, uint32_t slotmap, int k, uint32_t S,
     uint32_t nC, const uint32_t* __restrict__ entries, const uint16_t* __restrict__ tab,
     uint8_t* __restrict__ smask, int parts, const uint32_t* __restrict__ plan = nullptr,
@@ -1860,7 +1733,7 @@ __global__ __launch_bounds__(NT, DLSM_PROBE_MINWAVES) void probe_slice_kernel(
       for (int v = 0; v < V; v++) dst[min(static_cast<uint32_t>(v * NT + tid), nw - 1u)] = t[v];
       __syncthreads();
     };
-    walk_segments<U, CRU_C, uint4, DLSM_PROBE_DEPTH, DLSM_PROBE_NTL != 0>(
+    walk_segments<U, CRU_C, uint4, true>(
         tb, rowlen, entries, c_lo + wv * gs, NW * gs, c_hi, gs, walk_scr + wv * kWalkScratch, probe_set,
         slice_to_lds, CRU);
   } else {
@@ -1874,21 +1747,17 @@ __global__ __launch_bounds__(NT, DLSM_PROBE_MINWAVES) void probe_slice_kernel(
       for (int v = 0; v < V; v++) dst[min(static_cast<uint32_t>(v * NT + tid), nw - 1u)] = t[v];
     }
     __syncthreads();
-    walk_segments<U, CRU_C, uint4, DLSM_PROBE_DEPTH, DLSM_PROBE_NTL != 0>(
+    walk_segments<U, CRU_C, uint4, true>(
         tb, rowlen, entries, c_lo + wv * gs, NW * gs, c_hi, gs, walk_scr + wv * kWalkScratch, probe_set,
         NoPrologue{}, CRU);
   }
 }
 
-// Eight positions (16 bytes) of the unpermute: read once, non-temporal with
-// DLSM_PROBE_NTL (see SegWalk).
+// Eight positions (16 bytes) of the unpermute: read once, so non-temporal
+// like the slice pass's entry loads (see SegWalk).
 __device__ __forceinline__ uint4 load_pos8(const uint16_t* p) {
-#if DLSM_PROBE_NTL
   const u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
   return make_uint4(x.x, x.y, x.z, x.w);
-#else
-  return *reinterpret_cast<const uint4*>(p);
-#endif
 }
 
 // Pass 3: one workgroup per chunk: stage the chunk's bucketed answers in LDS
@@ -2023,19 +1892,29 @@ __device__ __forceinline__ void hash_full_chunk(const KeyDesc& kd, uint64_t firs
 // the next set (two sets of histograms alternate); after the scatter.  The
 // slices are 2^lgR lines (a power of two in the one-pass layout), so a line's
 // slice and offset are a shift and a mask.
-#ifndef DLSM_MG_PWAVES
-#define DLSM_MG_PWAVES 5  // partition: waves per SIMD the register budget must allow (A/B knob; 4: no spill, 1-2 % slower)
-#endif
-template <int MODE, int NT, int C, int P>
-__global__ __launch_bounds__(NT, DLSM_MG_PWAVES) void probe_mpartition_kernel(KeyDesc kd, const MGroupDev* __restrict__ groups,
-                                                              int G, uint32_t rowlen, uint32_t region,
-                                                              uint32_t* __restrict__ entries,
-                                                              uint16_t* __restrict__ pos,
-                                                              uint16_t* __restrict__ tab) {
+// One shape: kMGChunk keys, kMGPartBlock threads, kMGSetSize groups per set.
+// Global stores and what bounds each (mg_layout, bloom_capi.hip):
+//  * entries: [ereg + eoff_j, + hist[..][S_j]) -- the group's padded bucket
+//    total, <= mg_sub_entries(C, S_j), the sub-region mg_layout sums into
+//    `region` (and declines a set whose region passes the u16 offsets);
+//  * positions: [pos + (c * G + j) * C, + nk), nk <= C -- the caller sizes pos
+//    at chunks * G * C;
+//  * table: trow[tcol_j + b], b <= S_j -- tcol_j = sbase_j + j, so the last
+//    column is S_tot + G - 1 < rowlen.
+// Register budget for 5 waves per SIMD (4: no spill, but 1-2 % slower).
+constexpr int kMGPartWaves = 5;
+template <int MODE>
+__global__ __launch_bounds__(kMGPartBlock, kMGPartWaves) void probe_mpartition_kernel(
+    KeyDesc kd, const MGroupDev* __restrict__ groups, int G, uint32_t rowlen, uint32_t region,
+    uint32_t* __restrict__ entries, uint16_t* __restrict__ pos, uint16_t* __restrict__ tab) {
+  constexpr int NT = kMGPartBlock, C = kMGChunk, P = kMGSetSize;
   constexpr int PER = C / NT;
   constexpr int KB = mode_kb<MODE>();
   constexpr int QB = (kMaxSlices + 1 + 63) / 64;  // buckets per lane of a scanning wave
-  static_assert(PER % tile_kpt<KB>() == 0 && NT >= 64 * P, "chunk shape");
+  static_assert(PER % tile_kpt<KB>() == 0 && NT >= 64 * P, "chunk shape: wave p scans the set's group p");
+  static_assert(sizeof(uint16_t) * P * C + sizeof(uint32_t) * 2 * P * (kMaxSlices + 1) == 12304,
+                "static LDS (rk + hist) beside the dynamic tile / staging area");
+  static_assert(C + kMGPad * kMaxSlices <= 65536, "a group's entry indices (rk, table offsets) are u16");
   // key tiles, then the set's staged entries (group p of a set at the sum of
   // the earlier groups' C + 8 S): dynamic LDS sized by the launcher for the
   // filter set's largest set (mg_stage_bytes), so the occupancy follows the
@@ -2146,16 +2025,13 @@ __global__ __launch_bounds__(NT, DLSM_MG_PWAVES) void probe_mpartition_kernel(Ke
       }
     }
     __syncthreads();
-#ifndef DLSM_MG_ABL
-#define DLSM_MG_ABL 0  // ablation (timing only, wrong answers): 1 no entry stores, 2 no position stores
-#endif
     so = 0;
 #pragma unroll
     for (int pp = 0; pp < P; pp++) {
       if (pp >= np) break;
       const MGroupDev* gd = groups + j0 + pp;
-      if constexpr (!(DLSM_MG_ABL & 1)) store_chunk_u32<NT, true>(ereg + gd->eoff, stage + so, hist[P * q + pp][gd->S]);
-      if constexpr (!(DLSM_MG_ABL & 2)) store_chunk_u16<NT, true>(pos + (static_cast<uint64_t>(c) * G + j0 + pp) * C, rk[pp], nk);
+      store_chunk_u32<NT, true>(ereg + gd->eoff, stage + so, hist[P * q + pp][gd->S]);
+      store_chunk_u16<NT, true>(pos + (static_cast<uint64_t>(c) * G + j0 + pp) * C, rk[pp], nk);
       so += mg_sub_entries(C, gd->S);
     }
   }
@@ -3307,13 +3183,13 @@ hipError_t launch_full_partition(const FullJobDev* jobs, const uint32_t* chunk0s
 hipError_t launch_full_slices(const FullJobDev* jobs, const uint32_t* slice0s, int n_jobs,
                               uint32_t slice_first, uint32_t n_slices, const uint32_t* dchunk,
                               const uint32_t* entries, const uint16_t* tab, int lgR, hipStream_t s,
-                              uint32_t* crc_part, const uint32_t* crc_tabs, uint32_t* crc_cnt) {
+                              uint32_t* crc_part, const uint32_t* crc_tabs) {
   if (n_slices == 0) return hipSuccess;
 #define DLSM_FSL(LG)                                                                                          \
   do {                                                                                                        \
     if (crc_part)                                                                                             \
       full_slice_kernel<LG, true><<<n_slices, kSliceBlock, 0, s>>>(jobs, slice0s, n_jobs, dchunk, entries, tab, \
-                                                                   slice_first, crc_part, crc_tabs, crc_cnt);\
+                                                                   slice_first, crc_part, crc_tabs);         \
     else                                                                                                      \
       full_slice_kernel<LG, false><<<n_slices, kSliceBlock, 0, s>>>(jobs, slice0s, n_jobs, dchunk, entries,     \
                                                                     tab, slice_first);                       \
@@ -3332,7 +3208,7 @@ hipError_t launch_full_slices(const FullJobDev* jobs, const uint32_t* slice0s, i
 
 hipError_t launch_full_block_seal(const FullJobDev* jobs, int n_jobs, const uint32_t* crc_part,
                                   const uint32_t* crc_tabs, int lgR, hipStream_t s) {
-  if (n_jobs == 0 || DLSM_SEAL_LAST) return hipSuccess;  // the slices sealed the filters
+  if (n_jobs == 0) return hipSuccess;
   switch (lgR) {
     case 7: full_block_seal_kernel<7><<<n_jobs, 256, 0, s>>>(jobs, crc_part, crc_tabs); break;
     case 8: full_block_seal_kernel<8><<<n_jobs, 256, 0, s>>>(jobs, crc_part, crc_tabs); break;
@@ -3495,23 +3371,17 @@ static size_t device_lds_max(int dev) {
   return c;
 }
 
-#ifndef DLSM_PROBE_P13_HALF
-#define DLSM_PROBE_P13_HALF 1
-#endif
-#ifndef DLSM_PROBE_UNITS14
-#define DLSM_PROBE_UNITS14 2
-#endif
 // Probe chunk shapes: C keys per partition workgroup of NT threads.
-//   lgC 12: C = 4096, 512 threads;  13: 8192, 1024;  14: 16384, 1024.
+//   lgC 12: C = 4096, 512 threads;  13: 8192, 512 (H = 2 units);  14: 16384, 1024 (H = 2).
 template <int C, int NT, int H = 1>
 static hipError_t probe_partition_as(KeyDesc keys, uint32_t L, uint32_t magic, uint32_t R,
                                      uint32_t n_slices, uint32_t* entries, uint16_t* pos,
                                      uint16_t* tab, int mode, hipStream_t s, uint32_t cus) {
   const uint32_t nC = static_cast<uint32_t>((keys.n + C - 1) / C);
   if (nC == 0) return hipSuccess;
-  // One workgroup per chunk (default), or persistent: $DLSM_PART_GRID_PER_CU
-  // resident workgroups per CU looping over the chunks with the next chunk's
-  // key tiles in flight.  Round 4 (`profiles/r04_o_grid0_shares_ab.txt`): one
+  // One workgroup per chunk (per_cu 0), or persistent: per_cu resident
+  // workgroups per CU looping over the chunks with the next chunk's key tiles
+  // in flight.  Round 4 (`profiles/r04_o_grid0_shares_ab.txt`): one
   // workgroup per chunk takes the probe pass 0.685 -> 0.645 ms and the
   // overlapped step -4 % (the hardware's dispatcher keeps every CU's phases
   // mixed, with no tail of long-running workgroups and room for the build's
@@ -3521,40 +3391,25 @@ static hipError_t probe_partition_as(KeyDesc keys, uint32_t L, uint32_t magic, u
   // `profiles/r04_z_internal_keys_grid_ab.txt`) and hashed lookups (4 %
   // slower, `r04_z4_hashed_probe_grid_ab.txt`) keep the persistent grid, as
   // do variable-length keys (round 3's default, not re-measured).
-  static const int per_cu_env = [] {
-    const char* e = getenv("DLSM_PART_GRID_PER_CU");
-    return e ? atoi(e) : -1;
-  }();
-  const uint32_t per_cu = per_cu_env >= 0 ? static_cast<uint32_t>(per_cu_env) : (mode == KM_K20 ? 0u : 2u);
+  const uint32_t per_cu = mode == KM_K20 ? 0u : 2u;
   const uint32_t g = per_cu ? std::min(nC, per_cu * (cus ? cus : device_cus())) : nC;
-  // $DLSM_PROBE_PLAIN_STORES=1: plain (Infinity-Cache-allocating) intermediate
-  // stores, for round-sized batches (A/B knob; K20 keys only)
-  static const bool plain = [] {
-    const char* e = getenv("DLSM_PROBE_PLAIN_STORES");
-    return e && atoi(e) != 0;
-  }();
-#ifndef DLSM_PPART_PERSIST_ALWAYS
-#define DLSM_PPART_PERSIST_ALWAYS 0  // A/B: the persistent instantiation at every grid size
-#endif
-#define DLSM_PPART(MM, NTS_)                                                                                   \
-  do {                                                                                                         \
-    if (per_cu || DLSM_PPART_PERSIST_ALWAYS)                                                                   \
-      probe_partition_kernel<MM, NT, C, H, NTS_, true><<<g, NT, 0, s>>>(keys, L, magic, R, fastmod_magic(R),  \
-                                                                        n_slices, nC, entries, pos, tab);      \
-    else                                                                                                       \
-      probe_partition_kernel<MM, NT, C, H, NTS_, false><<<g, NT, 0, s>>>(keys, L, magic, R, fastmod_magic(R), \
-                                                                         n_slices, nC, entries, pos, tab);     \
+#define DLSM_PPART(MM)                                                                                   \
+  do {                                                                                                   \
+    if (per_cu)                                                                                          \
+      probe_partition_kernel<MM, NT, C, H, true><<<g, NT, 0, s>>>(keys, L, magic, R, fastmod_magic(R),  \
+                                                                  n_slices, nC, entries, pos, tab);      \
+    else                                                                                                 \
+      probe_partition_kernel<MM, NT, C, H, false><<<g, NT, 0, s>>>(keys, L, magic, R, fastmod_magic(R), \
+                                                                   n_slices, nC, entries, pos, tab);     \
   } while (0)
   if (mode == KM_HASH)
-    DLSM_PPART(KM_HASH, true);
-  else if (mode == KM_K20 && plain)
-    DLSM_PPART(KM_K20, false);
+    DLSM_PPART(KM_HASH);
   else if (mode == KM_K20)
-    DLSM_PPART(KM_K20, true);
+    DLSM_PPART(KM_K20);
   else if (mode == KM_K28)
-    DLSM_PPART(KM_K28, true);
+    DLSM_PPART(KM_K28);
   else
-    DLSM_PPART(KM_GENERIC, true);
+    DLSM_PPART(KM_GENERIC);
 #undef DLSM_PPART
   return hipGetLastError();
 }
@@ -3564,14 +3419,10 @@ hipError_t launch_probe_partition(KeyDesc keys, uint32_t L, uint32_t magic, uint
                                   uint16_t* tab, int mode, int lgC, hipStream_t s, uint32_t cus) {
   switch (lgC) {
     case 12: return probe_partition_as<4096, 512>(keys, L, magic, R, n_slices, entries, pos, tab, mode, s, cus);
-#if DLSM_PROBE_P13_HALF
     // 512-thread workgroups of two 4,096-key units (two resident per CU)
     case 13: return probe_partition_as<8192, 512, 2>(keys, L, magic, R, n_slices, entries, pos, tab, mode, s, cus);
-#else
-    case 13: return probe_partition_as<8192, 1024>(keys, L, magic, R, n_slices, entries, pos, tab, mode, s, cus);
-#endif
-    // 16,384-key chunks bucketed as two 8,192-key units (DLSM_PROBE_UNITS14)
-    case 14: return probe_partition_as<16384, 1024, DLSM_PROBE_UNITS14>(keys, L, magic, R, n_slices, entries, pos, tab, mode, s, cus);
+    // 16,384-key chunks bucketed as two 8,192-key units
+    case 14: return probe_partition_as<16384, 1024, 2>(keys, L, magic, R, n_slices, entries, pos, tab, mode, s, cus);
     default: return hipErrorInvalidValue;
   }
 }
@@ -3581,7 +3432,7 @@ static hipError_t probe_slices_as(const uint64_t* stacked, uint32_t L, uint32_t 
                                   uint32_t n_slices, uint32_t n_chunks, const uint32_t* entries,
                                   const uint16_t* tab, uint8_t* smask, int parts, hipStream_t s) {
   const uint8_t* st = reinterpret_cast<const uint8_t*>(stacked);
-  constexpr int NT = DLSM_PROBE_NT;
+  constexpr int NT = kProbeSliceBlock;
   if (R == 0 || R > (1u << LGR)) return hipErrorInvalidValue;
   if (k == 6)  // bits_per_key 10 (ChooseNumProbes)
     probe_slice_kernel<LGR, LGW, 6, NT, C><<<n_slices * parts, NT, 0, s>>>(
@@ -3743,16 +3594,12 @@ hipError_t launch_probe_unpermute_group(uint64_t n_keys, const uint16_t* pos, co
 }
 
 // ---- one-pass multi-group probe launchers ----------------------------------
-#ifndef DLSM_MG_NT
-#define DLSM_MG_NT 256  // partition threads per 2,048-key chunk
-#endif
-
 // Dynamic LDS of the one-pass partition: the key tiles or the largest set's
 // staged runs (stage_bytes, mg_layout), whichever is larger.
-template <int MODE, int NT, int C>
+template <int MODE>
 static size_t mg_part_lds(uint32_t stage_bytes) {
   constexpr int KB = MODE == KM_K28 ? 28 : 20;
-  using TL = K20Tile<NT, KB == 20 ? kTileKPT : 1, KB>;
+  using TL = K20Tile<kMGPartBlock, KB == 20 ? kTileKPT : 1, KB>;
   return std::max<size_t>(static_cast<size_t>(TL::kVec) * 16u, stage_bytes);
 }
 
@@ -3764,25 +3611,16 @@ hipError_t launch_probe_mpartition(KeyDesc keys, const MGroupDev* groups, int G,
   if (G < 1 || G > kMGMaxGroups || rowlen > kMGMaxSlices + kMGMaxGroups || region > 65535u ||
       region % kMGPad != 0)
     return hipErrorInvalidValue;
-  const int lgC = mg_chunk_lg(G);
-  const uint64_t nC64 = (keys.n + (1ull << lgC) - 1) >> lgC;
+  const uint64_t nC64 = (keys.n + kMGChunk - 1) >> kMGChunkLg;
   if (nC64 > 0xffffffffull) return hipErrorInvalidValue;
   const unsigned nC = static_cast<unsigned>(nC64);
-#define DLSM_MPART(MM, NT_, C_, P_)                                                                            \
-  probe_mpartition_kernel<MM, NT_, C_, P_><<<nC, NT_, mg_part_lds<MM, NT_, C_>(stage_bytes), s>>>(               \
+#define DLSM_MPART(MM)                                                                   \
+  probe_mpartition_kernel<MM><<<nC, kMGPartBlock, mg_part_lds<MM>(stage_bytes), s>>>(    \
       keys, groups, G, rowlen, region, entries, pos, tab)
-#define DLSM_MPART_C(NT_, C_, P_)                               \
-  do {                                                          \
-    if (mode == KM_K20) DLSM_MPART(KM_K20, NT_, C_, P_);        \
-    else if (mode == KM_K28) DLSM_MPART(KM_K28, NT_, C_, P_);   \
-    else if (mode == KM_HASH) DLSM_MPART(KM_HASH, NT_, C_, P_); \
-    else DLSM_MPART(KM_GENERIC, NT_, C_, P_);                   \
-  } while (0)
-  // (shapes: bloom_internal.h mg_chunk_lg; A/B knobs DLSM_MG_NT / DLSM_MG_P)
-  if (lgC == 12) DLSM_MPART_C(512, 4096, 2);
-  else if (lgC == 11) DLSM_MPART_C(DLSM_MG_NT, 2048, mg_set_size(11));
-  else return hipErrorInvalidValue;
-#undef DLSM_MPART_C
+  if (mode == KM_K20) DLSM_MPART(KM_K20);
+  else if (mode == KM_K28) DLSM_MPART(KM_K28);
+  else if (mode == KM_HASH) DLSM_MPART(KM_HASH);
+  else DLSM_MPART(KM_GENERIC);
 #undef DLSM_MPART
   return hipGetLastError();
 }
@@ -3792,7 +3630,7 @@ static hipError_t probe_mslices_as(const MGroupDev* groups, int G, uint32_t s0, 
                                    uint32_t region, uint32_t abytes, uint32_t n_chunks, const uint32_t* entries,
                                    const uint16_t* tab, uint8_t* answers, const uint32_t* plan, uint32_t wgs,
                                    hipStream_t s) {
-  constexpr int NT = DLSM_PROBE_NT;
+  constexpr int NT = kProbeSliceBlock;
   probe_slice_kernel<11 - LGW, LGW, K, NT, 0, 0u, true><<<wgs, NT, 0, s>>>(
       nullptr, 0u, 0u, 0u, 0, S, n_chunks, entries, tab, answers, 1, plan, groups, G, s0, rowlen, region, abytes);
   return hipGetLastError();
@@ -3824,38 +3662,27 @@ hipError_t launch_probe_munpermute(uint64_t n_keys, const MGroupDev* groups, int
                                    hipStream_t s) {
   if (n_keys == 0) return hipSuccess;
   if (mask_bytes < 1 || mask_bytes > 8 || abytes % 16u != 0 || abytes > 96u * 1024u) return hipErrorInvalidValue;
-  const int lgC = mg_chunk_lg(G);
-  const unsigned nC = static_cast<unsigned>((n_keys + (1ull << lgC) - 1) >> lgC);
+  const unsigned nC = static_cast<unsigned>((n_keys + kMGChunk - 1) >> kMGChunkLg);
   const uintptr_t a = reinterpret_cast<uintptr_t>(mask);
   const int mbv = (mask_bytes == 1 && (a & 7u) == 0) ? 1 : (mask_bytes == 2 && (a & 15u) == 0) ? 2 : 0;
   static std::atomic<uint64_t> attr{0};  // dynamic LDS past 64 KiB: once per device (idempotent)
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (abytes > 64u * 1024u && dev >= 0 && dev < 64 && !((attr.load() >> dev) & 1u)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&probe_munpermute_kernel<2048, 0>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&probe_munpermute_kernel<kMGChunk, 0>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&probe_munpermute_kernel<2048, 1>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&probe_munpermute_kernel<kMGChunk, 1>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&probe_munpermute_kernel<2048, 2>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&probe_munpermute_kernel<kMGChunk, 2>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     attr.fetch_or(uint64_t(1) << dev);
   }
-#define DLSM_MUNP(CC, MBV)                                                                                   \
-  probe_munpermute_kernel<CC, MBV><<<nC, kBlock, abytes, s>>>(n_keys, groups, G, abytes, pos, answers, mask, \
-                                                              mask_bytes)
-#define DLSM_MUNP_C(CC)                  \
-  do {                                   \
-    if (mbv == 1) DLSM_MUNP(CC, 1);      \
-    else if (mbv == 2) DLSM_MUNP(CC, 2); \
-    else DLSM_MUNP(CC, 0);               \
-  } while (0)
-  if (lgC == 12) {
-    if (abytes > 64u * 1024u) return hipErrorInvalidValue;
-    DLSM_MUNP_C(4096);
-  } else {
-    DLSM_MUNP_C(2048);
-  }
-#undef DLSM_MUNP_C
+#define DLSM_MUNP(MBV)                                                                                             \
+  probe_munpermute_kernel<kMGChunk, MBV><<<nC, kBlock, abytes, s>>>(n_keys, groups, G, abytes, pos, answers, mask, \
+                                                                    mask_bytes)
+  if (mbv == 1) DLSM_MUNP(1);
+  else if (mbv == 2) DLSM_MUNP(2);
+  else DLSM_MUNP(0);
 #undef DLSM_MUNP
   return hipGetLastError();
 }
@@ -3965,7 +3792,7 @@ hipError_t launch_version_slices(const uint8_t* image, uint32_t L, int k, uint32
                                  const uint32_t* plan, hipStream_t s) {
   if (n_chunks == 0) return hipSuccess;
   if (S < 1 || S > kVMaxSlices || L == 0) return hipErrorInvalidValue;
-  constexpr int NT = DLSM_PROBE_NT;
+  constexpr int NT = kProbeSliceBlock;
   constexpr uint32_t R = 1u << kVSliceLg;
   const uint32_t grid = S + kVPlanBudget;  // >= the plan's parts: sum max(1, ceil(u / target)) <= S + budget
   // packed image of one member (LGW 0): the filters' own line bytes, answer in bit 0

@@ -306,13 +306,9 @@ extern "C" int dlsm_bloom_hash_batch(const dlsm_keyset* keys, uint32_t* out, int
     hash_range(ks, 0, ks.n, out);
     return DLSM_OK;
   }
-  // the pool's threads go to the NUMA node that holds the keys ($DLSM_HASH_NUMA=0: left anywhere)
-  static const bool numa = [] {
-    const char* e = getenv("DLSM_HASH_NUMA");
-    return !(e && atoi(e) == 0);
-  }();
+  // the pool's threads go to the NUMA node that holds the keys
   const uint64_t key_bytes = ks.offsets ? ks.offsets[ks.n] : ks.n * static_cast<uint64_t>(ks.key_len);
-  const int node = numa ? numa_node_of(ks.bytes, key_bytes) : -1;
+  const int node = numa_node_of(ks.bytes, key_bytes);
   // `width` interleaved lanes of tasks: lane t takes parts t, t + width, ...
   pool.run(width, [&](int t) {
     for (uint64_t p = static_cast<uint64_t>(t); p < parts; p += static_cast<uint64_t>(width))
@@ -325,10 +321,6 @@ extern "C" int dlsm_host_read_bytes(const void* p, uint64_t n, int threads, uint
   if (!fold || threads < 0 || (n && !p) || (n & 7u)) return DLSM_E_ARG;
   *fold = 0;
   if (n == 0) return DLSM_OK;
-  static const bool numa = [] {
-    const char* e = getenv("DLSM_HASH_NUMA");
-    return !(e && atoi(e) == 0);
-  }();
   const uint64_t* w = static_cast<const uint64_t*>(p);
   const uint64_t words = n / 8;
   constexpr uint64_t kPart = 1u << 16;  // words per task (512 KiB)
@@ -354,7 +346,7 @@ extern "C" int dlsm_host_read_bytes(const void* p, uint64_t n, int threads, uint
     pool.run(width, [&](int t) {
       for (uint64_t q = static_cast<uint64_t>(t); q < parts; q += static_cast<uint64_t>(width))
         range(q * kPart, std::min(words, (q + 1) * kPart), acc[static_cast<size_t>(t) * 8]);
-    }, numa ? numa_node_of(p, n) : -1);
+    }, numa_node_of(p, n));
   }
   for (int t = 0; t < width; t++) *fold ^= acc[static_cast<size_t>(t) * 8];
   return DLSM_OK;

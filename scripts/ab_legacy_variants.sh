@@ -1,5 +1,5 @@
 #!/usr/bin/env bash
-# Interleaved A/B of library variants (make variant TAG=... VFLAGS=...) on the
+# Interleaved A/B of library variants (make variant TAG=...) on the
 # legacy-format batch build alone (scripts/bench_legacy.py), 3 rounds.
 #   bash scripts/ab_legacy_variants.sh base tag1 tag2 ...
 set -o pipefail

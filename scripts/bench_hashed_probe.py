@@ -41,8 +41,7 @@ def main(T=8, N=1_600_000, Q=100_000_000, reps=5):
         e[1].record(s)
         s.synchronize()
         ms = e[0].elapsed_time(e[1]) / reps
-        print(json.dumps({"probe_from": name, "grid_env": os.environ.get("DLSM_PART_GRID_PER_CU", "default"),
-                          "ms": round(ms, 4), "mkeys_s": round(Q / ms / 1e3, 1)}), flush=True)
+        print(json.dumps({"probe_from": name, "ms": round(ms, 4), "mkeys_s": round(Q / ms / 1e3, 1)}), flush=True)
     print(json.dumps({"masks_equal": bool(torch.equal(mask, mask2))}), flush=True)
 
 
