@@ -21,10 +21,12 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib as _L
-from ._lib import DlsmError, check, dlsm_build_job, dlsm_keyset
+from ._lib import (BLOCK_CHECKSUM, BLOCK_FILTER, BLOCK_OK, BLOCK_SHORT, BLOCK_TYPE, BlockError, DlsmError,
+                   check, dlsm_build_job, dlsm_keyset)
 
 __all__ = [
-    "Keys", "Context", "FilterSet", "DlsmError", "device_available", "bloom_hash",
+    "Keys", "Context", "FilterSet", "DlsmError", "BlockError", "BLOCK_OK", "BLOCK_SHORT", "BLOCK_CHECKSUM",
+    "BLOCK_TYPE", "BLOCK_FILTER", "device_available", "bloom_hash",
     "full_size", "legacy_size", "full_parse", "FullFilterBlockBuilder",
     "FullFilterBlockReader", "BloomFilterPolicy", "PATH_AUTO", "PATH_DIRECT", "PATH_SLICED",
     "crc32c", "crc32c_mask", "Version", "VersionFile",
@@ -233,7 +235,10 @@ class Version:
     level-0 newest first, then one candidate per level 1..5)."""
     NUM_LEVELS = 6
 
-    def __init__(self, ctx: "Context", files: Sequence[VersionFile], on_device: bool = False):
+    def __init__(self, ctx: "Context", files: Sequence[VersionFile], on_device: bool = False, *,
+                 sealed: bool = False, verify_checksums: bool = True):
+        """sealed: every file's ``filter`` is its sealed filter block (filter +
+        5-byte trailer), verified on the device; a bad block raises BlockError."""
         n = len(files)
         arr = (_L.dlsm_version_file * max(n, 1))()
         keep = []
@@ -253,8 +258,16 @@ class Version:
                                           len(f.largest), f.largest_trailer, f.number, f.level, 0,
                                           fp, fl)
         h = C.c_void_p()
-        check(lib().dlsm_version_create(ctx.h, arr, n, 1 if on_device else 0, C.byref(h)),
-              "version_create")
+        if sealed:
+            status = np.zeros(max(n, 1), dtype=np.uint8)
+            st = lib().dlsm_version_create_blocks(ctx.h, arr, n, 1 if on_device else 0,
+                                                  1 if verify_checksums else 0, status.ctypes.data, C.byref(h))
+            if st == _L.DLSM_E_CORRUPT:
+                raise BlockError(st, "version_create_blocks", status[:n])
+            check(st, "version_create_blocks")
+        else:
+            check(lib().dlsm_version_create(ctx.h, arr, n, 1 if on_device else 0, C.byref(h)),
+                  "version_create")
         self.h = h
         a, b = C.c_int(), C.c_int()
         check(lib().dlsm_version_slots(h, C.byref(a), C.byref(b)), "version_slots")
@@ -272,7 +285,10 @@ class Version:
 class FilterSet:
     """F parsed full filters resident on one device (FullFilterBlockReader state)."""
 
-    def __init__(self, ctx: "Context", filters, on_device: bool = False):
+    def __init__(self, ctx: "Context", filters, on_device: bool = False, *,
+                 sealed: bool = False, verify_checksums: bool = True):
+        """sealed: ``filters`` are sealed filter blocks (filter + 5-byte
+        trailer), verified on the device; a bad block raises BlockError."""
         self.ctx = ctx
         F = len(filters)
         if on_device:
@@ -285,12 +301,20 @@ class FilterSet:
             lens = [a.size for a in arrs]
             self._keep = arrs
         self.n_filters = F
-        self.lens = lens
+        self.lens = [max(n - 5, 0) for n in lens] if sealed else lens  # the filters' own lengths
         h = C.c_void_p()
         pa = (C.c_void_p * F)(*ptrs)
         la = (C.c_uint64 * F)(*lens)
-        check(lib().dlsm_filterset_create(ctx.h, pa, la, F, 1 if on_device else 0, C.byref(h)),
-              "filterset_create")
+        if sealed:
+            status = np.zeros(max(F, 1), dtype=np.uint8)
+            st = lib().dlsm_filterset_create_blocks(ctx.h, pa, la, F, 1 if on_device else 0,
+                                                    1 if verify_checksums else 0, status.ctypes.data, C.byref(h))
+            if st == _L.DLSM_E_CORRUPT:
+                raise BlockError(st, "filterset_create_blocks", status[:F])
+            check(st, "filterset_create_blocks")
+        else:
+            check(lib().dlsm_filterset_create(ctx.h, pa, la, F, 1 if on_device else 0, C.byref(h)),
+                  "filterset_create")
         self.h = h
         self._keep = None
 
@@ -479,6 +503,59 @@ class Context:
         check(lib().dlsm_bloom_full_build_block_dev(self.h, jobs, len(tables), bits_per_key,
                                                     _ptr(out_lens)), "full_build_block_dev")
 
+    def full_build_block_hashed(self, hash_sets, bits_per_key: int = 10, caps=None) -> list:
+        """Sealed filter blocks from BloomHash values (numpy uint32 arrays,
+        AddKey order) -- host in/out."""
+        sets = [np.ascontiguousarray(h, dtype=np.uint32) for h in hash_sets]
+        tables = [Keys(h if h.size else np.zeros(1, dtype=np.uint32), h.size, 4) for h in sets]
+        if caps is None:
+            caps = [full_size(h.size, bits_per_key)[0] + 5 for h in sets]
+        outs = [np.zeros(max(c, 1), dtype=np.uint8) for c in caps]
+        jobs = self._jobs(tables, outs, caps)
+        n = len(tables)
+        lens = (C.c_uint64 * max(n, 1))()
+        check(lib().dlsm_bloom_full_build_block_hashed(self.h, jobs, n, bits_per_key, lens),
+              "full_build_block_hashed")
+        return [outs[j][: lens[j]].tobytes() for j in range(n)]
+
+    def full_build_block_hashed_dev(self, hash_sets, outs, out_lens, bits_per_key: int = 10):
+        """Device form: hash_sets are device uint32 tensors, outs device slots."""
+        _need(out_lens, 8 * len(hash_sets), "full_build_block_hashed_dev out_lens")
+        tables = [Keys(h, int(h.numel()), 4) for h in hash_sets]
+        caps = [int(o.numel()) for o in outs]
+        jobs = self._jobs(tables, outs, caps)
+        check(lib().dlsm_bloom_full_build_block_hashed_dev(self.h, jobs, len(tables), bits_per_key,
+                                                           _ptr(out_lens)), "full_build_block_hashed_dev")
+
+    def blocks_check(self, blocks, on_device: bool = False, verify_checksums: bool = True) -> np.ndarray:
+        """ReadFilterBlock's trailer checks of sealed blocks of any contents
+        (bytes, or device uint8 tensors with on_device): uint8[n] of
+        BLOCK_OK / BLOCK_SHORT / BLOCK_CHECKSUM / BLOCK_TYPE."""
+        n = len(blocks)
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+        if on_device:
+            keep = list(blocks)
+            ptrs = [_ptr(b) if int(b.numel()) else None for b in keep]
+            lens = [int(b.numel()) for b in keep]
+        else:
+            keep = [np.frombuffer(bytes(b) + b"\0", dtype=np.uint8) for b in blocks]
+            ptrs = [a.ctypes.data for a in keep]
+            lens = [a.size - 1 for a in keep]
+        pa = (C.c_void_p * max(n, 1))(*ptrs)
+        la = (C.c_uint64 * max(n, 1))(*lens)
+        st = lib().dlsm_blocks_check(self.h, pa, la, n, 1 if on_device else 0, 1 if verify_checksums else 0,
+                                     status.ctypes.data)
+        if st != _L.DLSM_E_CORRUPT:
+            check(st, "blocks_check")
+        return status[:n]
+
+    def block_open_stats(self):
+        """(bytes read, bytes written, milliseconds between the events around
+        the two launches) of this context's last block check / open."""
+        r, w, ms = C.c_uint64(), C.c_uint64(), C.c_double()
+        check(lib().dlsm_block_open_stats(self.h, C.byref(r), C.byref(w), C.byref(ms)), "block_open_stats")
+        return int(r.value), int(w.value), float(ms.value)
+
     def crc32c_dev(self, bufs) -> list:
         """crc32c::Value of device tensors (uint8), computed on the GPU."""
         n = len(bufs)
@@ -538,8 +615,9 @@ class Context:
                                                 _ptr(block_offsets), _ptr(out)), "filter_block_probe_dev")
 
     # -- MultiGet-style probe of a version -------------------------------------
-    def version(self, files: Sequence[VersionFile], on_device: bool = False) -> Version:
-        return Version(self, files, on_device)
+    def version(self, files: Sequence[VersionFile], on_device: bool = False, *, sealed: bool = False,
+                verify_checksums: bool = True) -> Version:
+        return Version(self, files, on_device, sealed=sealed, verify_checksums=verify_checksums)
 
     def version_probe_dev(self, v: Version, keys: Keys, snapshot: int, slot_mask, level_file=None):
         """slot_mask (device uint64[n]): bit s = search slot s is a file Version::Get
@@ -550,8 +628,9 @@ class Context:
                                            _ptr(level_file)), "version_probe_dev")
 
     # -- full filter probe --------------------------------------------------
-    def filterset(self, filters, on_device: bool = False) -> FilterSet:
-        return FilterSet(self, filters, on_device)
+    def filterset(self, filters, on_device: bool = False, *, sealed: bool = False,
+                  verify_checksums: bool = True) -> FilterSet:
+        return FilterSet(self, filters, on_device, sealed=sealed, verify_checksums=verify_checksums)
 
     def full_probe(self, fs: FilterSet, keys: Keys) -> np.ndarray:
         mask = np.zeros(max(keys.n * fs.mask_bytes, 1), dtype=np.uint8)

@@ -56,6 +56,18 @@ class DlsmError(RuntimeError):
         super().__init__(f"{what}: {msg} ({status})" if what else f"{msg} ({status})")
 
 
+BLOCK_OK, BLOCK_SHORT, BLOCK_CHECKSUM, BLOCK_TYPE, BLOCK_FILTER = 0, 1, 2, 3, 4  # DLSM_BLOCK_*
+
+
+class BlockError(DlsmError):
+    """A sealed block failed ReadFilterBlock's checks: ``block_status`` holds
+    every block's DLSM_BLOCK_* outcome (uint8, the caller's order)."""
+
+    def __init__(self, status: int, what: str, block_status):
+        super().__init__(status, what)
+        self.block_status = block_status
+
+
 # Exported symbols and their signatures: (name, restype, argtypes).
 _VP = C.c_void_p
 _U64P = C.POINTER(C.c_uint64)
@@ -101,6 +113,14 @@ SIGNATURES = [
     ("dlsm_bloom_full_build", C.c_int, [_VP, C.POINTER(dlsm_build_job), C.c_int, C.c_int, _U64P]),
     ("dlsm_bloom_full_build_block_dev", C.c_int, [_VP, C.POINTER(dlsm_build_job), C.c_int, C.c_int, _VP]),
     ("dlsm_bloom_full_build_block", C.c_int, [_VP, C.POINTER(dlsm_build_job), C.c_int, C.c_int, _U64P]),
+    ("dlsm_bloom_full_build_block_hashed_dev", C.c_int, [_VP, C.POINTER(dlsm_build_job), C.c_int, C.c_int, _VP]),
+    ("dlsm_bloom_full_build_block_hashed", C.c_int, [_VP, C.POINTER(dlsm_build_job), C.c_int, C.c_int, _U64P]),
+    ("dlsm_blocks_check", C.c_int, [_VP, C.POINTER(_VP), _U64P, C.c_int, C.c_int, C.c_int, _VP]),
+    ("dlsm_block_open_stats", C.c_int, [_VP, _U64P, _U64P, C.POINTER(C.c_double)]),
+    ("dlsm_filterset_create_blocks", C.c_int, [_VP, C.POINTER(_VP), _U64P, C.c_int, C.c_int, C.c_int, _VP,
+                                               C.POINTER(_VP)]),
+    ("dlsm_version_create_blocks", C.c_int, [_VP, C.POINTER(dlsm_version_file), C.c_int, C.c_int, C.c_int,
+                                             _VP, C.POINTER(_VP)]),
     ("dlsm_crc32c_dev", C.c_int, [_VP, C.POINTER(_VP), _U64P, C.c_int, C.POINTER(C.c_uint32)]),
     ("dlsm_crc32c_extend", C.c_uint32, [C.c_uint32, _VP, C.c_size_t]),
     ("dlsm_crc32c_mask", C.c_uint32, [C.c_uint32]),

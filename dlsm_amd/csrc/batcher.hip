@@ -26,11 +26,18 @@
 
 #include "../../include/dlsm_bloom.h"
 
+// The sealed builds are weak references: the CPU test's stubbed ABI predates
+// them and links without (a DLSM_BATCH_SEALED job then answers DLSM_E_ARG).
+extern "C" {
+__attribute__((weak)) int dlsm_bloom_full_build_block(dlsm_ctx*, const dlsm_build_job*, int, int, uint64_t*);
+__attribute__((weak)) int dlsm_bloom_full_build_block_hashed(dlsm_ctx*, const dlsm_build_job*, int, int, uint64_t*);
+}
+
 namespace {
 struct Request {
   const dlsm_build_job* job;
   int bpk;
-  int flags;  // DLSM_BATCH_HASHED | DLSM_BATCH_EXACT
+  int flags;  // DLSM_BATCH_HASHED | DLSM_BATCH_EXACT | DLSM_BATCH_SEALED
   uint64_t out_len = 0;
   int status = DLSM_OK;
   bool done = false;
@@ -53,6 +60,10 @@ struct dlsm_batcher {
     // batch's builders saw repeated keys (their filters would otherwise take
     // the slice pass's re-hash fallback for a lowered line count)
     dlsm_ctx_set_option(ctx, DLSM_OPT_BUILD_EXACT, (flags & DLSM_BATCH_EXACT) ? 1 : 0);
+    if (flags & DLSM_BATCH_SEALED) {
+      auto* fn = (flags & DLSM_BATCH_HASHED) ? dlsm_bloom_full_build_block_hashed : dlsm_bloom_full_build_block;
+      return fn ? fn(ctx, jv, n, bpk, lens) : DLSM_E_ARG;
+    }
     return (flags & DLSM_BATCH_HASHED) ? dlsm_bloom_full_build_hashed(ctx, jv, n, bpk, lens)
                                        : dlsm_bloom_full_build(ctx, jv, n, bpk, lens);
   }
@@ -158,7 +169,7 @@ int dlsm_batcher_destroy(dlsm_batcher* b) {
 }
 
 int dlsm_batcher_submit(dlsm_batcher* b, const dlsm_build_job* job, int bits_per_key, int flags, uint64_t* out_len) {
-  if (!b || !job || !out_len || (flags & ~(DLSM_BATCH_HASHED | DLSM_BATCH_EXACT))) return DLSM_E_ARG;
+  if (!b || !job || !out_len || (flags & ~(DLSM_BATCH_HASHED | DLSM_BATCH_EXACT | DLSM_BATCH_SEALED))) return DLSM_E_ARG;
   Request r{job, bits_per_key, flags};
   std::unique_lock<std::mutex> lk(b->m);
   if (b->stop) return DLSM_E_ARG;

@@ -171,6 +171,14 @@ struct dlsm_ctx {
   DevBuf<uint8_t*> crc_outp;
   DevBuf<uint64_t> crc_cap;
   DevBuf<uint32_t> crc_val;
+  // sealed-block ingest (block_ingest.hip): descriptors, part prefix sums,
+  // per-part crcs, per-block records; the events time its two launches
+  DevBuf<IngestBlock> ing_blocks;
+  DevBuf<uint32_t> ing_part0;
+  DevBuf<uint32_t> ing_partial;
+  DevBuf<IngestRecord> ing_rec;
+  hipEvent_t ev_ing0 = nullptr, ev_ing1 = nullptr;
+  uint64_t ing_read = 0, ing_written = 0;  // bytes of the last ingest
   // internal-key selection / gather: [blk_cnt | blk_bytes | tot(2) | first_bad]
   DevBuf<uint64_t> sel;
   // host-API results: page-locked, device-mapped, so the build kernels store
@@ -676,6 +684,12 @@ int dlsm_ctx_destroy(dlsm_ctx* ctx) {
   ctx->crc_outp.release();
   ctx->crc_cap.release();
   ctx->crc_val.release();
+  ctx->ing_blocks.release();
+  ctx->ing_part0.release();
+  ctx->ing_partial.release();
+  ctx->ing_rec.release();
+  if (ctx->ev_ing0) (void)hipEventDestroy(ctx->ev_ing0);
+  if (ctx->ev_ing1) (void)hipEventDestroy(ctx->ev_ing1);
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_wait) (void)hipEventDestroy(ctx->ev_wait);
   if (ctx->ev_pfork) (void)hipEventDestroy(ctx->ev_pfork);
@@ -1431,8 +1445,8 @@ int run_crc(dlsm_ctx* ctx, const std::vector<std::vector<uint8_t>>& streams, int
 }
 }  // namespace
 
-int dlsm_bloom_full_build_block_dev(dlsm_ctx* ctx, const dlsm_build_job* jobs, int n_jobs,
-                                    int bits_per_key, uint64_t* out_len_dev) {
+static int build_block_dev_impl(dlsm_ctx* ctx, const dlsm_build_job* jobs, int n_jobs, int bits_per_key,
+                                uint64_t* out_len_dev, bool hashed) {
   if (!ctx || n_jobs < 0 || (n_jobs > 0 && (!jobs || !out_len_dev))) return DLSM_E_ARG;
   if (n_jobs == 0) return DLSM_OK;
   DeviceGuard g(ctx->device);
@@ -1450,15 +1464,25 @@ int dlsm_bloom_full_build_block_dev(dlsm_ctx* ctx, const dlsm_build_job* jobs, i
   // the sliced build seals its own filters (the crc fused into its slice
   // pass); the direct path takes the separate crc passes below
   bool sealed = false;
-  DLSM_CHECK(full_build_dev_impl(ctx, fj.data(), n_jobs, bits_per_key, out_len_dev, false, true, &sealed));
+  DLSM_CHECK(full_build_dev_impl(ctx, fj.data(), n_jobs, bits_per_key, out_len_dev, hashed, true, &sealed));
   if (sealed) return DLSM_OK;
   std::vector<std::vector<uint8_t>> st(n_jobs, std::vector<uint8_t>(crc_stream_size()));
   for (int j = 0; j < n_jobs; j++) crc_stream_fill(st[j].data(), jobs[j].out, out_len_dev + j, 0, 1);
   return run_crc(ctx, st, n_jobs, max_total, outs.data(), caps.data(), out_len_dev, nullptr);
 }
 
-int dlsm_bloom_full_build_block(dlsm_ctx* ctx, const dlsm_build_job* jobs, int n_jobs,
-                                int bits_per_key, uint64_t* out_len) {
+int dlsm_bloom_full_build_block_dev(dlsm_ctx* ctx, const dlsm_build_job* jobs, int n_jobs,
+                                    int bits_per_key, uint64_t* out_len_dev) {
+  return build_block_dev_impl(ctx, jobs, n_jobs, bits_per_key, out_len_dev, false);
+}
+
+int dlsm_bloom_full_build_block_hashed_dev(dlsm_ctx* ctx, const dlsm_build_job* jobs, int n_jobs,
+                                           int bits_per_key, uint64_t* out_len_dev) {
+  return build_block_dev_impl(ctx, jobs, n_jobs, bits_per_key, out_len_dev, true);
+}
+
+static int build_block_host_impl(dlsm_ctx* ctx, const dlsm_build_job* jobs, int n_jobs, int bits_per_key,
+                                 uint64_t* out_len, bool hashed) {
   if (!ctx || n_jobs < 0 || (n_jobs > 0 && (!jobs || !out_len))) return DLSM_E_ARG;
   if (n_jobs == 0) return DLSM_OK;
   DeviceGuard g(ctx->device);
@@ -1484,7 +1508,7 @@ int dlsm_bloom_full_build_block(dlsm_ctx* ctx, const dlsm_build_job* jobs, int n
   DLSM_CHECK(ctx->st_out.ensure(obytes + 256));
   DLSM_CHECK(ctx->st_len.ensure(n_jobs));
   for (int j = 0; j < n_jobs; j++) dj[j].out = ctx->st_out.p + opos[j];
-  DLSM_CHECK(dlsm_bloom_full_build_block_dev(ctx, dj.data(), n_jobs, bits_per_key, ctx->st_len.p));
+  DLSM_CHECK(build_block_dev_impl(ctx, dj.data(), n_jobs, bits_per_key, ctx->st_len.p, hashed));
   hipStream_t s = ctx->stream;
   DLSM_TRY(hipMemcpyAsync(out_len, ctx->st_len.p, sizeof(uint64_t) * n_jobs, hipMemcpyDeviceToHost, s));
   DLSM_TRY(ctx_sync(ctx, s));
@@ -1498,6 +1522,16 @@ int dlsm_bloom_full_build_block(dlsm_ctx* ctx, const dlsm_build_job* jobs, int n
   }
   DLSM_TRY(ctx_sync(ctx, s));
   return st;
+}
+
+int dlsm_bloom_full_build_block(dlsm_ctx* ctx, const dlsm_build_job* jobs, int n_jobs,
+                                int bits_per_key, uint64_t* out_len) {
+  return build_block_host_impl(ctx, jobs, n_jobs, bits_per_key, out_len, false);
+}
+
+int dlsm_bloom_full_build_block_hashed(dlsm_ctx* ctx, const dlsm_build_job* jobs, int n_jobs,
+                                       int bits_per_key, uint64_t* out_len) {
+  return build_block_host_impl(ctx, jobs, n_jobs, bits_per_key, out_len, true);
 }
 
 int dlsm_crc32c_dev(dlsm_ctx* ctx, const uint8_t* const* bufs, const uint64_t* lens, int n,
@@ -1516,6 +1550,110 @@ int dlsm_crc32c_dev(dlsm_ctx* ctx, const uint8_t* const* bufs, const uint64_t* l
   DLSM_CHECK(run_crc(ctx, st, n, max_total, nullptr, nullptr, nullptr, ctx->crc_val.p));
   DLSM_TRY(hipMemcpyAsync(crc_out, ctx->crc_val.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
   DLSM_TRY(ctx_sync(ctx, ctx->stream));
+  return DLSM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Sealed blocks, read side: ReadFilterBlock (table/format.cc:380-444) for n
+// blocks in two launches (block_ingest.hip)
+// ---------------------------------------------------------------------------
+static_assert(DLSM_BLOCK_OK == DLSM_INGEST_OK && DLSM_BLOCK_SHORT == DLSM_INGEST_SHORT &&
+                  DLSM_BLOCK_CHECKSUM == DLSM_INGEST_CHECKSUM && DLSM_BLOCK_TYPE == DLSM_INGEST_TYPE &&
+                  DLSM_BLOCK_FILTER == DLSM_INGEST_FILTER,
+              "block outcomes");
+namespace {
+// Verify (and copy, where dst differs from src) the device-resident blocks
+// `blk`; recs gets one record per block.  One upload of the work list, two
+// launches, one D2H, one synchronisation.
+int run_ingest(dlsm_ctx* ctx, const std::vector<IngestBlock>& blk, bool verify, bool parse,
+               std::vector<IngestRecord>& recs) {
+  const size_t n = blk.size();
+  recs.assign(n, IngestRecord{});
+  if (n == 0) return DLSM_OK;
+  if (n > 0x7fffffffull) return DLSM_E_ARG;
+  hipStream_t s = ctx->stream;
+  std::vector<uint32_t> part0(n + 1);
+  uint64_t parts = 0, rd = 0, wr = 0;
+  for (size_t j = 0; j < n; j++) {
+    part0[j] = static_cast<uint32_t>(parts);
+    parts += ingest_block_parts(blk[j].len);
+    if (parts > 0x7fffffffull) return DLSM_E_ARG;
+    if (blk[j].len >= 5) {
+      const bool store = blk[j].dst && blk[j].dst != blk[j].src;
+      if (store || verify) rd += blk[j].len;
+      if (store) wr += blk[j].len - 5;
+    }
+  }
+  part0[n] = static_cast<uint32_t>(parts);
+  DLSM_CHECK(ctx->ing_blocks.ensure(n));
+  DLSM_CHECK(ctx->ing_part0.ensure(n + 1));
+  DLSM_CHECK(ctx->ing_partial.ensure(parts));
+  DLSM_CHECK(ctx->ing_rec.ensure(n));
+  if (!ctx->ev_ing0) DLSM_TRY(hipEventCreate(&ctx->ev_ing0));
+  if (!ctx->ev_ing1) DLSM_TRY(hipEventCreate(&ctx->ev_ing1));
+  DLSM_CHECK(ctx_upload(ctx, ctx->ing_blocks.p, blk.data(), sizeof(IngestBlock) * n, s));
+  DLSM_CHECK(ctx_upload(ctx, ctx->ing_part0.p, part0.data(), sizeof(uint32_t) * (n + 1), s));
+  DLSM_TRY(hipEventRecord(ctx->ev_ing0, s));
+  DLSM_TRY(launch_block_ingest(ctx->ing_blocks.p, ctx->ing_part0.p, static_cast<uint32_t>(n),
+                               static_cast<uint32_t>(parts), verify, parse, ctx->ing_partial.p, ctx->ing_rec.p, s));
+  DLSM_TRY(hipEventRecord(ctx->ev_ing1, s));
+  DLSM_TRY(hipMemcpyAsync(recs.data(), ctx->ing_rec.p, sizeof(IngestRecord) * n, hipMemcpyDeviceToHost, s));
+  DLSM_TRY(ctx_sync(ctx, s));
+  ctx->ing_read = rd;
+  ctx->ing_written = wr;
+  return DLSM_OK;
+}
+
+// status[j] (when given) for every record; DLSM_E_CORRUPT if any is not OK.
+int ingest_status(const std::vector<IngestRecord>& recs, const std::vector<int>& where, uint8_t* status) {
+  int st = DLSM_OK;
+  for (size_t j = 0; j < recs.size(); j++) {
+    if (status) status[where.empty() ? j : static_cast<size_t>(where[j])] = static_cast<uint8_t>(recs[j].status);
+    if (recs[j].status != DLSM_BLOCK_OK) st = DLSM_E_CORRUPT;
+  }
+  return st;
+}
+}  // namespace
+
+int dlsm_blocks_check(dlsm_ctx* ctx, const uint8_t* const* blocks, const uint64_t* lens, int n,
+                      int blocks_are_device, int verify_checksums, uint8_t* status) {
+  if (!ctx || n < 0 || (n > 0 && (!blocks || !lens || !status))) return DLSM_E_ARG;
+  if (n == 0) return DLSM_OK;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = ctx->stream;
+  std::vector<IngestBlock> blk(n);
+  uint64_t bytes = 0;
+  for (int j = 0; j < n; j++) {
+    if (lens[j] && !blocks[j]) return DLSM_E_ARG;
+    blk[j] = IngestBlock{blocks[j], nullptr, lens[j]};
+    bytes += (lens[j] + 255) & ~uint64_t(255);
+  }
+  if (!blocks_are_device) {
+    DLSM_CHECK(ctx->st_filter.ensure(bytes + 256));
+    uint64_t off = 0;
+    for (int j = 0; j < n; j++) {
+      blk[j].src = ctx->st_filter.p + off;
+      if (lens[j]) DLSM_TRY(hipMemcpyAsync(ctx->st_filter.p + off, blocks[j], lens[j], hipMemcpyHostToDevice, s));
+      off += (lens[j] + 255) & ~uint64_t(255);
+    }
+  }
+  std::vector<IngestRecord> recs;
+  DLSM_CHECK(run_ingest(ctx, blk, verify_checksums != 0, false, recs));
+  return ingest_status(recs, {}, status);
+}
+
+int dlsm_block_open_stats(const dlsm_ctx* ctx, uint64_t* bytes_read, uint64_t* bytes_written, double* kernel_ms) {
+  if (!ctx) return DLSM_E_ARG;
+  if (bytes_read) *bytes_read = ctx->ing_read;
+  if (bytes_written) *bytes_written = ctx->ing_written;
+  if (kernel_ms) {
+    *kernel_ms = 0;
+    if (ctx->ev_ing0 && ctx->ev_ing1) {
+      float ms = 0;
+      DLSM_TRY(hipEventElapsedTime(&ms, ctx->ev_ing0, ctx->ev_ing1));
+      *kernel_ms = ms;
+    }
+  }
   return DLSM_OK;
 }
 
@@ -1707,8 +1845,16 @@ hipError_t mg_layout(dlsm_filterset* fs, hipStream_t s) {
 }  // namespace
 extern "C" {
 
-int dlsm_filterset_create(dlsm_ctx* ctx, const uint8_t* const* filters, const uint64_t* lens,
-                          int n_filters, int filters_are_device, dlsm_filterset** out) {
+// How the *_create_blocks calls hand their inputs to the create code: the
+// pointers are sealed blocks, verified and parsed on the device.
+struct BlocksArg {
+  bool verify;
+  uint8_t* status;  // host u8 per block in the caller's order, or nullptr
+};
+
+static int filterset_create_impl(dlsm_ctx* ctx, const uint8_t* const* filters, const uint64_t* lens,
+                                 int n_filters, int filters_are_device, const BlocksArg* ba,
+                                 dlsm_filterset** out) {
   if (!ctx || !out || !filters || !lens || n_filters < 1 || n_filters > 64) return DLSM_E_ARG;
   *out = nullptr;
   DeviceGuard g(ctx->device);
@@ -1717,7 +1863,14 @@ int dlsm_filterset_create(dlsm_ctx* ctx, const uint8_t* const* filters, const ui
   std::vector<FilterDev> h(n_filters);
   std::vector<uint64_t> off(n_filters);
   uint64_t blob = 0;
-  for (int f = 0; f < n_filters; f++) {
+  for (int f = 0; f < n_filters && ba; f++) {
+    // sealed blocks: the device pass below reads the tails; a slot holds the
+    // whole block (host blocks are verified in place)
+    if (lens[f] && !filters[f]) return DLSM_E_ARG;
+    off[f] = blob;
+    blob += (lens[f] + 255) & ~uint64_t(255);
+  }
+  for (int f = 0; f < n_filters && !ba; f++) {
     if (!filters[f] || lens[f] < 5) return DLSM_E_CORRUPT;
     uint8_t tail[5];
     const uint8_t* tp = filters[f] + lens[f] - 5;
@@ -1748,7 +1901,27 @@ int dlsm_filterset_create(dlsm_ctx* ctx, const uint8_t* const* filters, const ui
     dlsm_filterset_destroy(fs);
     return from_hip(e);
   }
-  for (int f = 0; f < n_filters; f++) {
+  if (ba) {
+    // host blocks: one copy to the slot, then the pass runs in place
+    std::vector<IngestBlock> blk(n_filters);
+    for (int f = 0; f < n_filters; f++) {
+      blk[f] = IngestBlock{filters[f], fs->blob + off[f], lens[f]};
+      if (filters_are_device) continue;
+      blk[f].src = blk[f].dst;
+      if (lens[f]) e = hipMemcpyAsync(blk[f].dst, filters[f], lens[f], hipMemcpyHostToDevice, s);
+      if (e != hipSuccess) break;
+    }
+    std::vector<IngestRecord> recs;
+    int st = e == hipSuccess ? run_ingest(ctx, blk, ba->verify, true, recs) : from_hip(e);
+    if (st == DLSM_OK) st = ingest_status(recs, {}, ba->status);
+    if (st != DLSM_OK) {
+      dlsm_filterset_destroy(fs);
+      return st;
+    }
+    for (int f = 0; f < n_filters; f++)
+      h[f] = FilterDev{fs->blob + off[f], recs[f].L, recs[f].magic, recs[f].k, recs[f].lg};
+  }
+  for (int f = 0; f < n_filters && !ba; f++) {
     e = hipMemcpyAsync(fs->blob + off[f], filters[f], lens[f],
                        filters_are_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
     if (e != hipSuccess) break;
@@ -1818,6 +1991,18 @@ int dlsm_filterset_create(dlsm_ctx* ctx, const uint8_t* const* filters, const ui
   }
   *out = fs;
   return DLSM_OK;
+}
+
+int dlsm_filterset_create(dlsm_ctx* ctx, const uint8_t* const* filters, const uint64_t* lens,
+                          int n_filters, int filters_are_device, dlsm_filterset** out) {
+  return filterset_create_impl(ctx, filters, lens, n_filters, filters_are_device, nullptr, out);
+}
+
+int dlsm_filterset_create_blocks(dlsm_ctx* ctx, const uint8_t* const* blocks, const uint64_t* lens,
+                                 int n_filters, int blocks_are_device, int verify_checksums, uint8_t* status,
+                                 dlsm_filterset** out) {
+  const BlocksArg ba{verify_checksums != 0, status};
+  return filterset_create_impl(ctx, blocks, lens, n_filters, blocks_are_device, &ba, out);
 }
 
 int dlsm_filterset_destroy(dlsm_filterset* fs) {
@@ -2323,8 +2508,8 @@ uint64_t version_slice_min_bytes() {
 }
 }  // namespace
 
-int dlsm_version_create(dlsm_ctx* ctx, const dlsm_version_file* files, int n_files,
-                        int filters_are_device, dlsm_version** out) {
+static int version_create_impl(dlsm_ctx* ctx, const dlsm_version_file* files, int n_files,
+                               int filters_are_device, const BlocksArg* ba, dlsm_version** out) {
   if (!ctx || !out || n_files < 0 || (n_files > 0 && !files)) return DLSM_E_ARG;
   *out = nullptr;
   DeviceGuard g(ctx->device);
@@ -2433,7 +2618,7 @@ int dlsm_version_create(dlsm_ctx* ctx, const dlsm_version_file* files, int n_fil
   uint64_t total = files_bytes + pre_bytes + keys_bytes + bnd_bytes + ivl_bytes;
   for (int j = 0; j < n_files; j++) {
     const dlsm_version_file& F = files[order[j]];
-    if (!F.filter) continue;
+    if (!F.filter || ba) continue;  // sealed blocks: the device pass reads the tails
     if (F.filter_len < 5) return DLSM_E_CORRUPT;
     uint8_t tail[5];
     if (filters_are_device) {
@@ -2456,7 +2641,9 @@ int dlsm_version_create(dlsm_ctx* ctx, const dlsm_version_file* files, int n_fil
   int32_t lvl_sliced[kNumLevels];
   std::vector<uint64_t> copy_len(n_files, 0);
   for (int lv = 0; lv < kNumLevels; lv++) lvl_sliced[lv] = -1;
-  const uint64_t min_bytes = ctx->vslice_bytes == 0 ? version_slice_min_bytes()
+  // (from sealed blocks the line counts are not known before the layout: no level is sliced)
+  const uint64_t min_bytes = ba ? 0
+                             : ctx->vslice_bytes == 0 ? version_slice_min_bytes()
                              : (ctx->vslice_bytes == UINT64_MAX ? 0 : ctx->vslice_bytes);
   for (int lv = 1; lv < kNumLevels && min_bytes; lv++) {
     uint64_t lines = 0;
@@ -2502,7 +2689,35 @@ int dlsm_version_create(dlsm_ctx* ctx, const dlsm_version_file* files, int n_fil
   ver->device = ctx->device;
   ver->n_files = n_files;
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&ver->mem), std::max<uint64_t>(total, 256));
-  for (int j = 0; j < n_files && e == hipSuccess; j++) {
+  if (ba && e == hipSuccess) {
+    // one verify-and-ingest pass over every file's block (search order);
+    // host blocks are copied to their slots first and verified in place
+    std::vector<IngestBlock> blk;
+    std::vector<int> where, slot;
+    for (int j = 0; j < n_files && e == hipSuccess; j++) {
+      const dlsm_version_file& F = files[order[j]];
+      if (ba->status) ba->status[order[j]] = DLSM_BLOCK_OK;
+      if (!F.filter) continue;
+      IngestBlock b{F.filter, ver->mem + foff[j], F.filter_len};
+      if (!filters_are_device) {
+        b.src = b.dst;
+        if (F.filter_len) e = hipMemcpyAsync(b.dst, F.filter, F.filter_len, hipMemcpyHostToDevice, s);
+      }
+      blk.push_back(b);
+      where.push_back(order[j]);
+      slot.push_back(j);
+    }
+    std::vector<IngestRecord> recs;
+    int st = e == hipSuccess ? run_ingest(ctx, blk, ba->verify, true, recs) : from_hip(e);
+    if (st == DLSM_OK) st = ingest_status(recs, where, ba->status);
+    if (st != DLSM_OK) {
+      dlsm_version_destroy(ver);
+      return st;
+    }
+    for (size_t q = 0; q < blk.size(); q++)
+      h[slot[q]].f = FilterDev{blk[q].dst, recs[q].L, recs[q].magic, recs[q].k, recs[q].lg};
+  }
+  for (int j = 0; j < n_files && e == hipSuccess && !ba; j++) {
     const dlsm_version_file& F = files[order[j]];
     if (!F.filter) continue;
     h[j].f.data = ver->mem + foff[j];
@@ -2555,6 +2770,18 @@ int dlsm_version_create(dlsm_ctx* ctx, const dlsm_version_file* files, int n_fil
   }
   *out = ver;
   return DLSM_OK;
+}
+
+int dlsm_version_create(dlsm_ctx* ctx, const dlsm_version_file* files, int n_files,
+                        int filters_are_device, dlsm_version** out) {
+  return version_create_impl(ctx, files, n_files, filters_are_device, nullptr, out);
+}
+
+int dlsm_version_create_blocks(dlsm_ctx* ctx, const dlsm_version_file* files, int n_files,
+                               int blocks_are_device, int verify_checksums, uint8_t* status,
+                               dlsm_version** out) {
+  const BlocksArg ba{verify_checksums != 0, status};
+  return version_create_impl(ctx, files, n_files, blocks_are_device, &ba, out);
 }
 
 int dlsm_version_destroy(dlsm_version* v) {

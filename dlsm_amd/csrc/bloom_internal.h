@@ -374,4 +374,34 @@ hipError_t launch_crc_streams(const void* streams, int n, int max_parts, uint32_
                               uint8_t* const* seal_out, const uint64_t* seal_cap, uint64_t* seal_len,
                               uint32_t* crc_out, hipStream_t s);
 
+// block_ingest.hip: verify-and-ingest of n sealed blocks (ReadFilterBlock).
+// One block: `len` bytes at src (any alignment); its len - 5 content bytes go
+// to dst unless dst is nullptr or equals src.
+struct IngestBlock {
+  const uint8_t* src;
+  uint8_t* dst;
+  uint64_t len;
+};
+// Per-block outcome (DLSM_BLOCK_* of the public header) and, for filter
+// blocks, what parse_tail reads from the content's tail.
+enum : uint32_t {
+  DLSM_INGEST_OK = 0,
+  DLSM_INGEST_SHORT = 1,
+  DLSM_INGEST_CHECKSUM = 2,
+  DLSM_INGEST_TYPE = 3,
+  DLSM_INGEST_FILTER = 4
+};
+struct IngestRecord {
+  uint32_t status;
+  int32_t k;
+  uint32_t L;
+  int32_t lg;
+  uint32_t magic;
+};
+// Parts (workgroups) block of `len` bytes takes; part0 holds the n + 1 prefix
+// sums, partial one u32 per part, rec one record per block.
+uint64_t ingest_block_parts(uint64_t len);
+hipError_t launch_block_ingest(const IngestBlock* blocks, const uint32_t* part0, uint32_t n, uint32_t total_parts,
+                               bool verify, bool parse, uint32_t* partial, IngestRecord* rec, hipStream_t s);
+
 }  // namespace dlsm

@@ -300,9 +300,12 @@ int dlsm_batcher_full_build_hashed(dlsm_batcher* b, const dlsm_build_job* job, i
  * bucketing, DLSM_OPT_BUILD_EXACT = 1).  Jobs are batched only with jobs of
  * the same bits_per_key and flags.  A job whose batch fails for another
  * reason than a small slot is re-run alone, so each caller gets its own
- * status. */
+ * status.  DLSM_BATCH_SEALED: the executor builds the sealed filter block
+ * (dlsm_bloom_full_build_block[_hashed]): the slot needs 5 more bytes and
+ * out_len counts them. */
 #define DLSM_BATCH_HASHED 1
 #define DLSM_BATCH_EXACT 2
+#define DLSM_BATCH_SEALED 4
 int dlsm_batcher_submit(dlsm_batcher* b, const dlsm_build_job* job, int bits_per_key, int flags,
                         uint64_t* out_len);
 /* Batches run, jobs built, and the largest batch so far. */
@@ -317,6 +320,13 @@ int dlsm_bloom_full_build_block_dev(dlsm_ctx* ctx, const dlsm_build_job* jobs, i
                                     int bits_per_key, uint64_t* out_len_dev);
 int dlsm_bloom_full_build_block(dlsm_ctx* ctx, const dlsm_build_job* jobs, int n_jobs,
                                 int bits_per_key, uint64_t* out_len);
+/* The sealed build from BloomHash values (keys as dlsm_bloom_full_build_hashed*
+ * takes them): what a builder with the reference's AddKey (hash_entries_)
+ * hands over in FinishFilterBlock. */
+int dlsm_bloom_full_build_block_hashed_dev(dlsm_ctx* ctx, const dlsm_build_job* jobs, int n_jobs,
+                                           int bits_per_key, uint64_t* out_len_dev);
+int dlsm_bloom_full_build_block_hashed(dlsm_ctx* ctx, const dlsm_build_job* jobs, int n_jobs,
+                                       int bits_per_key, uint64_t* out_len);
 
 /* crc32c::Value of n device buffers on the GPU (ReadFilterBlock's check,
  * table/format.cc:398-408); crc_out: host uint32[n].  Synchronous. */
@@ -325,6 +335,32 @@ int dlsm_crc32c_dev(dlsm_ctx* ctx, const uint8_t* const* bufs, const uint64_t* l
 /* Host helpers: crc32c::Extend and crc32c::Mask (util/crc32c.h:17-31). */
 uint32_t dlsm_crc32c_extend(uint32_t init_crc, const void* data, size_t n);
 uint32_t dlsm_crc32c_mask(uint32_t crc);
+
+/* ---- sealed blocks, read side (ReadFilterBlock, table/format.cc:380-444) -- */
+
+/* Per-block outcomes, in the order the reference makes its checks. */
+#define DLSM_BLOCK_OK 0
+#define DLSM_BLOCK_SHORT 1    /* < 5 bytes: no trailer (format.cc:389 would underflow) */
+#define DLSM_BLOCK_CHECKSUM 2 /* format.cc:398-407 "block checksum mismatch" */
+#define DLSM_BLOCK_TYPE 3     /* format.cc:410-441 "bad block type" (type byte != 0) */
+#define DLSM_BLOCK_FILTER 4   /* contents FullFilterBlockReader's ctor rejects or cannot probe
+                                 (what dlsm_bloom_full_parse answers DLSM_E_CORRUPT for) */
+
+/* The block-trailer check of n blocks of any contents, each
+ * [contents][type][Fixed32(crc32c::Mask(crc32c(contents || type)))], on the
+ * GPU in two launches whatever n is.  blocks_are_device: device pointers on
+ * ctx's device (any alignment; 16-byte-aligned blocks are read with 16-byte
+ * loads), else host memory.  verify_checksums = 0 skips the crc compare
+ * (ReadOptions::verify_checksums).  status (host u8[n]) is always filled with
+ * DLSM_BLOCK_OK / SHORT / CHECKSUM / TYPE; returns DLSM_OK when every block
+ * passes, else DLSM_E_CORRUPT.  Synchronous. */
+int dlsm_blocks_check(dlsm_ctx* ctx, const uint8_t* const* blocks, const uint64_t* lens, int n,
+                      int blocks_are_device, int verify_checksums, uint8_t* status);
+
+/* Bytes the last block check / open of ctx read and wrote on the device and
+ * the time between the events around its two launches (any may be NULL). */
+int dlsm_block_open_stats(const dlsm_ctx* ctx, uint64_t* bytes_read, uint64_t* bytes_written,
+                          double* kernel_ms);
 
 /* ---- internal keys: the flush / compaction loops that feed AddKey -------- */
 
@@ -370,6 +406,17 @@ int dlsm_user_keys_gather_dev(dlsm_ctx* ctx, const dlsm_keyset* ikeys, const uin
  * pointers already resident on ctx's device.  The set keeps its own copy. */
 int dlsm_filterset_create(dlsm_ctx* ctx, const uint8_t* const* filters, const uint64_t* lens,
                           int n_filters, int filters_are_device, dlsm_filterset** out);
+/* The same set from the F sealed filter blocks a reader holds (what
+ * ReadFilterBlock fetched, e.g. dlsm_bloom_full_build_block[_dev]'s output):
+ * one device pass copies each block's contents into the set, re-computes and
+ * compares its crc32c (unless verify_checksums = 0), checks its type byte and
+ * parses the filter -- one synchronisation, no per-block round trip.  status
+ * (host u8[F] or NULL) receives every block's DLSM_BLOCK_* outcome.  If any
+ * block is not OK: *out = NULL and DLSM_E_CORRUPT.  The set answers every
+ * probe exactly as one created from the stripped filters. */
+int dlsm_filterset_create_blocks(dlsm_ctx* ctx, const uint8_t* const* blocks, const uint64_t* lens,
+                                 int n_filters, int blocks_are_device, int verify_checksums, uint8_t* status,
+                                 dlsm_filterset** out);
 int dlsm_filterset_destroy(dlsm_filterset* fs);
 int dlsm_filterset_size(const dlsm_filterset* fs, int* n_filters, uint64_t* device_bytes);
 
@@ -434,6 +481,18 @@ typedef struct dlsm_version dlsm_version; /* the files and filters, resident on 
  * where it exit(1)s or cannot probe). */
 int dlsm_version_create(dlsm_ctx* ctx, const dlsm_version_file* files, int n_files,
                         int filters_are_device, dlsm_version** out);
+/* dlsm_version_create from sealed filter blocks: files[i].filter / filter_len
+ * describe file i's sealed block (NULL still means a table without a filter;
+ * its status is DLSM_BLOCK_OK).  Every block is verified, stripped and parsed
+ * in one device pass for any n_files.  status (host u8[n_files] or NULL) is
+ * indexed by the caller's file order, not by search order.  If any block is
+ * not OK: *out = NULL and DLSM_E_CORRUPT.  A version opened from blocks
+ * ignores DLSM_OPT_VERSION_SLICE_BYTES: every level is probed directly (the
+ * line counts a sliced level's image is laid out by are not known before the
+ * device pass). */
+int dlsm_version_create_blocks(dlsm_ctx* ctx, const dlsm_version_file* files, int n_files,
+                               int blocks_are_device, int verify_checksums, uint8_t* status,
+                               dlsm_version** out);
 int dlsm_version_destroy(dlsm_version* v);
 /* Search slots: 0 .. n_l0-1 = level-0 files newest first (largest number
  * first); n_l0 + level - 1 = the one candidate file of level 1..5. */

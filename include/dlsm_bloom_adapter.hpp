@@ -11,8 +11,10 @@
 //       (: FilterPolicy) -- internal keys, hashed as ExtractUserKey(key)
 //   FullFilterBlockBuilder  table/full_filter_block.h:33-70
 //       (RestartBlock AddKey*)* Finish; Reset; Move_buffer; public `result`
+//       + FinishBlock: Finish and FinishFilterBlock's trailer in one step
 //   FullFilterBlockReader   table/full_filter_block.h:71-94
 //       ctor parses metadata; KeyMayMatch; + KeysMayMatch (batch)
+//       + FromBlock: ReadFilterBlock's checks (host::ReadFilterBlock), then the ctor
 //   FilterBlockBuilder      table/filter_block.h:34-68 (legacy 2 KiB framing)
 //       StartBlock AddKey* ... Finish; public `result`
 //   FilterBlockReader       table/filter_block.h:70-85
@@ -48,6 +50,7 @@
 #include <immintrin.h>
 #endif
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "dlsm_bloom.h"
@@ -306,6 +309,37 @@ inline uint64_t MatchAllFilter(int bits_per_key, char* out, size_t cap) {
   out[64] = static_cast<char>(dlsm_bloom_full_num_probes(bits_per_key));
   PutFixed32(out + 65, 1);
   return kMatchAllLen;
+}
+
+// The block trailer FinishFilterBlock appends (table/table_builder_computeside.cc:
+// 418-428, kBlockTrailerSize table/format.h): [type kNoCompression = 0]
+// [Fixed32(crc32c::Mask(crc32c::Value(contents || type)))] behind the len
+// content bytes at out (room for 5 more).  Returns len + 5.
+constexpr size_t kBlockTrailerSize = 5;
+inline uint64_t SealBlock(char* out, uint64_t len) {
+  out[len] = 0;
+  const uint32_t crc = dlsm_crc32c_extend(0, out, static_cast<size_t>(len) + 1);
+  PutFixed32(out + len + 1, dlsm_crc32c_mask(crc));
+  return len + kBlockTrailerSize;
+}
+
+// ReadFilterBlock's checks (table/format.cc:389-441) on a sealed block held in
+// host memory, in the reference's order: the trailer must be there, then (when
+// verify_checksums) the stored crc must match crc32c::Value(contents || type),
+// then the type byte must be kNoCompression.  Returns a DLSM_BLOCK_* code;
+// on DLSM_BLOCK_OK *contents is the block without its trailer.
+inline int ReadFilterBlock(const Slice& block, bool verify_checksums, Slice* contents) {
+  if (block.size() < kBlockTrailerSize) return DLSM_BLOCK_SHORT;
+  const size_t n = block.size() - kBlockTrailerSize;
+  const char* data = block.data();
+  if (verify_checksums) {
+    // Mask is a bijection: comparing masked values is comparing Unmask(stored) with the crc
+    const uint32_t actual = dlsm_crc32c_mask(dlsm_crc32c_extend(0, data, n + 1));
+    if (actual != GetFixed32(data + n + 1)) return DLSM_BLOCK_CHECKSUM;
+  }
+  if (data[n] != 0) return DLSM_BLOCK_TYPE;
+  if (contents) *contents = Slice(data, n);
+  return DLSM_BLOCK_OK;
 }
 
 // The parsed metadata of a full filter (FullFilterBlockReader ctor,
@@ -603,7 +637,18 @@ class FullFilterBlockBuilder {
   }
   // full_filter_block.cc:93-141 -- writes the filter into result.data()'s
   // buffer (the slot, or the buffer given to Move_buffer).
-  void Finish() { finish_impl(); }
+  void Finish() { finish_impl<false>(); }
+  // FinishFilterBlock in one step (table/table_builder_computeside.cc:389-432):
+  // Finish, but `result` is the sealed block -- the filter, the type byte and
+  // the masked crc32c, the bytes FlushFilter RDMA-writes -- so the buffer
+  // needs 5 more bytes and the caller appends nothing.  The crc is computed
+  // on the GPU with the filter (dlsm_bloom_full_build_block[_hashed], or the
+  // batcher's DLSM_BATCH_SEALED); the host fallback seals with
+  // dlsm_crc32c_extend / dlsm_crc32c_mask.  When the buffer cannot hold the
+  // sealed filter, the sealed match-everything filter (74 bytes) goes in its
+  // place with status DLSM_E_CAPACITY (empty below 74 bytes), so the table
+  // stays readable.
+  void FinishBlock() { finish_impl<true>(); }
   void Reset() { result.Reset(static_cast<char*>(local_mr_->addr), 0); }
 
  private:
@@ -653,9 +698,21 @@ class FullFilterBlockBuilder {
     last_len_ = key.size();
     n_++;
   }
+  // The match-everything filter at out, sealed as a block when Seal.
+  template <bool Seal>
+  uint64_t match_all(char* out, size_t cap) const {
+    if constexpr (Seal) {
+      if (cap < host::kMatchAllLen + host::kBlockTrailerSize) return 0;
+      return host::SealBlock(out, host::MatchAllFilter(bits_per_key_, out, cap - host::kBlockTrailerSize));
+    } else {
+      return host::MatchAllFilter(bits_per_key_, out, cap);
+    }
+  }
+  // Seal: FinishBlock -- the sealed entry points, and a sealed result.
+  template <bool Seal>
   void finish_impl() {
     if (reference_addkey_) {
-      finish_hash_entries();
+      finish_hash_entries<Seal>();
       return;
     }
     if (opt_.hash_in_addkey && pend_n_) hash_pending();
@@ -665,8 +722,7 @@ class FullFilterBlockBuilder {
       // only sense a Bloom filter must be -- no false negatives
       device_status_ = status_ = stage_status_;
       fell_back_ = false;
-      result.Reset(result.data(), host::MatchAllFilter(bits_per_key_, const_cast<char*>(result.data()),
-                                                       output_capacity()));
+      result.Reset(result.data(), match_all<Seal>(const_cast<char*>(result.data()), output_capacity()));
       clear_keys();
       return;
     }
@@ -698,14 +754,19 @@ class FullFilterBlockBuilder {
     }
     if (opt_.batcher)  // the flag tells the batcher's executor context to count exactly
       status_ = dlsm_batcher_submit(opt_.batcher, &job, bits_per_key_,
-                                    (opt_.hash_in_addkey ? DLSM_BATCH_HASHED : 0) | (dups_ ? DLSM_BATCH_EXACT : 0), &len);
+                                    (opt_.hash_in_addkey ? DLSM_BATCH_HASHED : 0) | (dups_ ? DLSM_BATCH_EXACT : 0) |
+                                        (Seal ? DLSM_BATCH_SEALED : 0),
+                                    &len);
+    else if constexpr (Seal)
+      status_ = opt_.hash_in_addkey ? dlsm_bloom_full_build_block_hashed(ctx_, &job, 1, bits_per_key_, &len)
+                                    : dlsm_bloom_full_build_block(ctx_, &job, 1, bits_per_key_, &len);
     else if (opt_.hash_in_addkey)
       status_ = dlsm_bloom_full_build_hashed(ctx_, &job, 1, bits_per_key_, &len);
     else
       status_ = dlsm_bloom_full_build(ctx_, &job, 1, bits_per_key_, &len);
     if (own_exact) dlsm_ctx_set_option(ctx_, DLSM_OPT_BUILD_EXACT, exact);
     if (!ctx_ && !opt_.batcher) status_ = DLSM_E_DEVICE;
-    settle(status_, len, [&](std::vector<uint32_t>& h) { staged_hashes(h); });
+    settle<Seal>(status_, len, [&](std::vector<uint32_t>& h) { staged_hashes(h); });
     clear_keys();
   }
   // The BloomHash values of the staged keys, in AddKey order (the host
@@ -730,7 +791,9 @@ class FullFilterBlockBuilder {
   // match-everything filter goes in its place (status DLSM_E_CAPACITY).  The
   // result is never a 0-byte or partial filter unless the buffer cannot hold
   // even that one (fewer than 69 bytes, or Move_buffer without a size).
-  template <class GetHashes>
+  // Seal (FinishBlock): len counts the block trailer, and the host's filters
+  // are sealed on the host.
+  template <bool Seal, class GetHashes>
   void settle(int st, uint64_t len, GetHashes get_hashes) {
     device_status_ = st;
     fell_back_ = false;
@@ -746,7 +809,11 @@ class FullFilterBlockBuilder {
       fell_back_ = true;
       std::vector<uint32_t> h;
       get_hashes(h);
-      len = host::FullFilterFromHashes(h.data(), h.size(), bits_per_key_, out, cap, true);
+      const size_t room = Seal ? (cap >= host::kBlockTrailerSize ? cap - host::kBlockTrailerSize : 0) : cap;
+      len = host::FullFilterFromHashes(h.data(), h.size(), bits_per_key_, out, room, true);
+      if constexpr (Seal) {
+        if (len) len = host::SealBlock(out, len);
+      }
       if (len) {
         status_ = DLSM_OK;
         result.Reset(result.data(), len);
@@ -754,7 +821,7 @@ class FullFilterBlockBuilder {
       }
     }
     status_ = DLSM_E_CAPACITY;
-    result.Reset(result.data(), host::MatchAllFilter(bits_per_key_, out, cap));
+    result.Reset(result.data(), match_all<Seal>(out, cap));
   }
 
  public:
@@ -791,6 +858,7 @@ class FullFilterBlockBuilder {
   // Finish of the reference-signature form: the filter of hash_entries_
   // (CalculateSpace + AddHash + trailer, full_filter_block.cc:93-141) built
   // on the GPU from the 4-byte hashes.
+  template <bool Seal>
   void finish_hash_entries() {
     dlsm_build_job job;
     job.keys.bytes = reinterpret_cast<const uint8_t*>(hash_entries_.data());
@@ -801,8 +869,13 @@ class FullFilterBlockBuilder {
     job.out = reinterpret_cast<uint8_t*>(const_cast<char*>(result.data()));
     job.out_cap = output_capacity();
     uint64_t len = 0;
-    const int st = ctx_ ? dlsm_bloom_full_build_hashed(ctx_, &job, 1, bits_per_key_, &len) : DLSM_E_DEVICE;
-    settle(st, len, [&](std::vector<uint32_t>& h) { h.assign(hash_entries_.begin(), hash_entries_.end()); });
+    int st = DLSM_E_DEVICE;
+    if constexpr (Seal) {
+      if (ctx_) st = dlsm_bloom_full_build_block_hashed(ctx_, &job, 1, bits_per_key_, &len);
+    } else {
+      if (ctx_) st = dlsm_bloom_full_build_hashed(ctx_, &job, 1, bits_per_key_, &len);
+    }
+    settle<Seal>(st, len, [&](std::vector<uint32_t>& h) { h.assign(hash_entries_.begin(), hash_entries_.end()); });
     hash_entries_.clear();
   }
   // BloomHash of the pending keys into the staged hashes, dropping a hash
@@ -964,6 +1037,31 @@ class FullFilterBlockReader {
   }
   FullFilterBlockReader(const FullFilterBlockReader&) = delete;
   FullFilterBlockReader& operator=(const FullFilterBlockReader&) = delete;
+
+  // The reader of a sealed filter block as ReadFilterBlock fetched it
+  // (table/format.cc:380-444 followed by the constructor, as
+  // Table::ReadFilter does): host::ReadFilterBlock's checks, then a reader
+  // over the block's contents (the block's bytes stay the caller's, like a
+  // filter's).  *block_status (may be null) gets the DLSM_BLOCK_* code; a
+  // block that fails the checks gives nullptr.  Delete the reader with
+  // `delete`.
+  static FullFilterBlockReader* FromBlock(const Slice& block, bool verify_checksums, dlsm_ctx* ctx,
+                                          int* block_status = nullptr) {
+    Slice contents;
+    const int st = host::ReadFilterBlock(block, verify_checksums, &contents);
+    if (block_status) *block_status = st;
+    return st == DLSM_BLOCK_OK ? new FullFilterBlockReader(contents, ctx) : nullptr;
+  }
+  // The same with the reference constructor's arguments (Side: the host's
+  // FilterSide enum, never a pointer -- that is the form above).
+  template <class M, class Side, class = typename std::enable_if<!std::is_pointer<Side>::value>::type>
+  static FullFilterBlockReader* FromBlock(const Slice& block, bool verify_checksums, M rdma_mg, Side side,
+                                          int* block_status = nullptr) {
+    Slice contents;
+    const int st = host::ReadFilterBlock(block, verify_checksums, &contents);
+    if (block_status) *block_status = st;
+    return st == DLSM_BLOCK_OK ? new FullFilterBlockReader(contents, rdma_mg, side) : nullptr;
+  }
 
   // full_filter_block.cc:269-284, on the host.
   bool KeyMayMatch(const Slice& key) const {
