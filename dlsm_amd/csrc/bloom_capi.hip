@@ -17,8 +17,10 @@
 
 #include "../../include/dlsm_bloom.h"
 #include "bloom_internal.h"
+#include "host_plan.h"
 
 using namespace dlsm;
+using namespace dlsm::plan;
 
 namespace {
 
@@ -72,8 +74,6 @@ struct DevBuf {
 
 bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
-uint32_t ceil_div_u32(uint64_t a, uint64_t b) { return static_cast<uint32_t>((a + b - 1) / b); }
-
 }  // namespace
 
 // Pipelined passes (opt-in knobs).  Probe: round r+1's partition runs on a
@@ -84,7 +84,6 @@ uint32_t ceil_div_u32(uint64_t a, uint64_t b) { return static_cast<uint32_t>((a 
 // Off by default: measured on MI355X (profiles/r01_v12_*), the overlapped
 // kernels each ran ~2x slower (the slice passes fill every wave slot of a CU)
 // and every round added ~10 us of launch gaps, a net loss.
-constexpr int kProbeBufs = 3;
 constexpr int kStageEvents = 4;
 
 // The scheduling options a pooled context starts with; a recycled context gets
@@ -218,31 +217,6 @@ struct dlsm_ctx {
   hipEvent_t ev_wait = nullptr;      // ctx_sync modes 1 and 2
 };
 
-// A stacked image of the filters of one mask byte that share a line count
-// and probe count (at most 8): filter f answers in bit f % 8 of byte f / 8.
-// A group of 1, 2 or 3-4 filters gets a packed image instead (W = 1, 2 or 4
-// bits per bit position, 64 * W bytes per line: 8 / 4 / 2 times the lines per
-// LDS slice), so a large single filter -- the biggest file of a level -- still
-// fits the sliced path, and small groups walk fewer, longer bucket runs.
-struct ProbeGroup {
-  uint64_t* stacked = nullptr;  // L * 8 * 2^lgw u64 words
-  uint32_t L = 0, magic = 0;
-  int k = 0;
-  int mask_byte = 0;
-  bool first_of_byte = false;  // writes its mask byte; later groups of the byte OR into it
-  int lgw = 3;                  // log2 bits per bit position of the image (3: stacked bytes)
-  uint32_t slotmap = 0;         // packed images: member m answers in bit (slotmap >> 4m) & 7
-};
-
-// One image-width class of a one-pass multi-group probe: the global slices
-// [s0, s0 + S) of the groups with image width lgw, walked by one slice launch
-// of wgs workgroups (plan: S + 1 workgroup starts at d_mgplan + plan_off).
-struct MGClass {
-  int lgw = 0, K = 0;  // K: 6 when every group of the class has k = 6, else 0 (run time k)
-  uint32_t s0 = 0, S = 0;
-  uint32_t plan_off = 0, wgs = 0;
-};
-
 struct dlsm_filterset {
   int device = 0;
   int F = 0;
@@ -302,16 +276,6 @@ int validate_keyset(const dlsm_keyset& k) {
   return DLSM_OK;
 }
 
-KeyDesc to_desc(const dlsm_keyset& k) {
-  KeyDesc d;
-  d.bytes = k.bytes;
-  d.offsets = k.offsets;
-  d.n = k.n;
-  d.key_len = k.key_len;
-  d.suffix = k.suffix_len;
-  return d;
-}
-
 // The K20 kernels stage keys through LDS with 16-byte loads.
 bool is_k20(const dlsm_keyset& k) {
   return k.offsets == nullptr && k.key_len == 20 && k.suffix_len == 0 &&
@@ -323,36 +287,6 @@ bool is_k20(const dlsm_keyset& k) {
 bool is_k28(const dlsm_keyset& k) {
   return k.offsets == nullptr && k.key_len == 28 && k.suffix_len == 8 &&
          (k.n == 0 || aligned(k.bytes, 16));
-}
-
-// Slice width for the sliced build: the smallest 2^lgR (lgR in [9, 11]) that
-// keeps every job at <= kMaxSlices slices, then narrower (down to 2^7 lines,
-// 8 KiB) while the batch has fewer than two slice workgroups per CU -- a
-// batch of dLSM-sized flush tables (153,846 keys, 3,005 lines) would
-// otherwise leave most CUs idle.  Returns -1 if none fits.
-int choose_build_lgR(const std::vector<uint32_t>& Ls) {
-  auto slices = [&](int lg, uint64_t* total) {
-    bool ok = true;
-    *total = 0;
-    for (uint32_t L : Ls) {
-      const uint64_t n = (static_cast<uint64_t>(L) + (1u << lg) - 1) >> lg;
-      ok = ok && n <= kMaxSlices;
-      *total += std::max<uint64_t>(n, 1);
-    }
-    return ok;
-  };
-  uint64_t total = 0, t2 = 0;
-  // the slice-workgroup count below which the slices narrow: two per CU
-  constexpr uint64_t min_wgs = 2ull * kBuildSliceCUs;
-  for (int lg = 9; lg <= 11; lg++) {  // widest-first search from 2^9 lines (32 KiB slices)
-    if (!slices(lg, &total)) continue;
-    while (lg > 7 && total < min_wgs && slices(lg - 1, &t2)) {
-      lg--;
-      total = t2;
-    }
-    return lg;
-  }
-  return -1;
 }
 
 // The helper stream starts behind everything already queued on the context
@@ -382,32 +316,6 @@ int join_part(dlsm_ctx* ctx) {
 int hand_over(hipStream_t from, hipStream_t to, hipEvent_t ev) {
   DLSM_TRY(hipEventRecord(ev, from));
   DLSM_TRY(hipStreamWaitEvent(to, ev, 0));
-  return DLSM_OK;
-}
-
-// FullFilterBlockReader ctor checks (table/full_filter_block.cc:186-252) on the
-// filter's 5-byte tail and total length.
-int parse_tail(const uint8_t* tail, uint64_t len64, int* k_out, uint32_t* L_out, int* lg_out) {
-  if (len64 < 5 || len64 > 0xffffffffull) return DLSM_E_CORRUPT;
-  const int k = static_cast<int>(static_cast<int8_t>(tail[0]));
-  if (k < 1) return DLSM_E_CORRUPT;  // the reference exit(1)s
-  const uint32_t len = static_cast<uint32_t>(len64) - 5;
-  const uint32_t L = uint32_t(tail[1]) | (uint32_t(tail[2]) << 8) | (uint32_t(tail[3]) << 16) |
-                     (uint32_t(tail[4]) << 24);
-  int lg;
-  if (L * kCacheLineBytes == len) {
-    // common case; L == 0 (empty filter) would make KeyMayMatch divide by 0,
-    // and a wrapped product would index past the filter
-    if (L == 0 || static_cast<uint64_t>(L) * kCacheLineBytes != len) return DLSM_E_CORRUPT;
-    lg = 6;
-  } else if (L == 0 || len % L != 0) {
-    return DLSM_E_CORRUPT;  // the reference exit(1)s
-  } else {
-    lg = 0;  // log2_cache_line_size_ keeps its initialiser (full_filter_block.h:85)
-  }
-  *k_out = k;
-  *L_out = L;
-  *lg_out = lg;
   return DLSM_OK;
 }
 
@@ -1073,7 +981,6 @@ int full_build_dev_impl(dlsm_ctx* ctx, const dlsm_build_job* jobs, int n_jobs, i
   if (ctx->fault) return -ctx->fault;
   if (n_jobs == 0) return DLSM_OK;
   DeviceGuard g(ctx->device);
-  const int k = full_num_probes(bits_per_key);
   std::vector<uint32_t> Ls(n_jobs);
   bool all_k20 = true, all_k28 = true, sliced_ok = ctx->path != 1;
   for (int j = 0; j < n_jobs; j++) {
@@ -1104,37 +1011,11 @@ int full_build_dev_impl(dlsm_ctx* ctx, const dlsm_build_job* jobs, int n_jobs, i
   const bool exact = sliced_ok && (hashed || ctx->build_exact == 1 ||
                                    (ctx->build_exact == 0 && (any_suffix || mode == KM_GENERIC)));
 
-  std::vector<FullJobDev> hj(n_jobs);
-  std::vector<uint32_t> starts(2 * n_jobs);
-  uint64_t entry = 0, tabw = 0;
-  uint32_t chunk = 0, slice = 0;
-  for (int j = 0; j < n_jobs; j++) {
-    const dlsm_build_job& b = jobs[j];
-    FullJobDev& d = hj[j];
-    d.keys = to_desc(b.keys);
-    d.out = b.out;
-    d.out_cap = b.out_cap;
-    d.out_len = out_len_dev + j;
-    d.entry0 = entry;
-    d.n_chunks = ceil_div_u32(b.keys.n, kBuildChunk);
-    d.chunk0 = chunk;
-    d.L_spec = Ls[j];
-    d.magic_spec = Ls[j] ? fastmod_magic(Ls[j]) : 0;
-    d.n_slices = sliced_ok ? std::max<uint32_t>(1, ceil_div_u32(Ls[j], 1ull << lgR)) : 1;
-    d.slice0 = slice;
-    d.tab0 = tabw;
-    d.k = k;
-    d.bpk = bits_per_key;
-    d.exact = exact ? 1 : 0;
-    d.reserved = 0;
-    starts[j] = chunk;
-    starts[n_jobs + j] = slice;
-    // chunk regions of kBuildRegion entries (buckets padded to 16-byte units)
-    entry += static_cast<uint64_t>(d.n_chunks) * kBuildRegion;
-    chunk += d.n_chunks;
-    slice += d.n_slices;
-    tabw += static_cast<uint64_t>(d.n_slices + 1) * d.n_chunks;
-  }
+  const JobTable<FullJobDev> T = plan_full_jobs(jobs, n_jobs, bits_per_key, out_len_dev, Ls, lgR, sliced_ok, exact);
+  const std::vector<FullJobDev>& hj = T.hj;
+  const std::vector<uint32_t>& starts = T.starts;
+  const uint64_t entry = T.entry, tabw = T.tabw;
+  const uint32_t chunk = T.chunk, slice = T.slice;
   hipStream_t s = ctx->stream;
   const bool same = ctx->last_jobs.size() == hj.size() && ctx->last_starts == starts &&
                     memcmp(ctx->last_jobs.data(), hj.data(), sizeof(FullJobDev) * n_jobs) == 0 &&
@@ -1175,10 +1056,7 @@ int full_build_dev_impl(dlsm_ctx* ctx, const dlsm_build_job* jobs, int n_jobs, i
     // runs on the helper stream while the context stream runs group g-1's
     // slices (LDS-bound).
     const int G = std::max(1, std::min(ctx->build_groups, n_jobs));
-    std::vector<int> cut(1, 0);
-    for (int j = 1; j < n_jobs && static_cast<int>(cut.size()) < G; j++)
-      if (static_cast<uint64_t>(starts[j]) * G >= static_cast<uint64_t>(chunk) * cut.size()) cut.push_back(j);
-    cut.push_back(n_jobs);
+    const std::vector<int> cut = job_group_cuts(starts, chunk, n_jobs, G);
     const int ng = static_cast<int>(cut.size()) - 1;
     auto chunk_at = [&](int j) { return j < n_jobs ? starts[j] : chunk; };
     auto slice_at = [&](int j) { return j < n_jobs ? starts[n_jobs + j] : slice; };
@@ -1726,121 +1604,34 @@ uint32_t device_cus_of(int dev) {
   return static_cast<uint32_t>(n);
 }
 
-// The one-pass layout of a multi-group set (bloom_internal.h, MGroupDev): the
-// groups ordered by image width (one slice launch per width), every group cut
-// into full 128 KiB slices (2^(11 - lgw) lines), the slices numbered globally.
-// Each width class gets a workgroup plan over the CUs: a slice's share of the
-// workgroups is its share of the class's entries -- every lookup has one entry
-// per group, so slice s of group j (nl_s of L_j lines) expects nl_s / L_j of
-// them (a 3-slice group's slices get ~10x the workgroups of a 30-slice
-// group's).  A set that does not fit (a group with more than 256 slices, more
-// than kMGMaxSlices in all) keeps the per-group passes.  `s` is synchronised by
-// the caller before the host tables go out of scope.
-hipError_t mg_layout(dlsm_filterset* fs, hipStream_t s) {
-  const int G = static_cast<int>(fs->groups.size());
-  std::vector<int> order(G);
-  for (int j = 0; j < G; j++) order[j] = j;
-  std::stable_sort(order.begin(), order.end(),
-                   [&](int a, int b) { return fs->groups[a].lgw < fs->groups[b].lgw; });
-  std::vector<MGroupDev> md;
-  uint32_t sbase = 0;
-  for (int j : order) {
-    const ProbeGroup& g = fs->groups[j];
-    const uint32_t R = 1u << (11 - g.lgw);
-    const uint32_t S = ceil_div_u32(g.L, R);
-    if (S < 1 || S > static_cast<uint32_t>(kMaxSlices) || !g.stacked) return hipSuccess;
-    MGroupDev d{};
-    d.image = reinterpret_cast<const uint8_t*>(g.stacked);
-    d.L = g.L;
-    d.magic = g.magic;
-    d.R = R;
-    d.rmagic = fastmod_magic(R);
-    d.S = S;
-    d.sbase = sbase;
-    d.slotmap = g.slotmap;
-    d.k = g.k;
-    d.lgw = g.lgw;
-    d.mask_byte = g.mask_byte;
-    md.push_back(d);
-    sbase += S;
+// The one-pass layout of a multi-group set (plan_mg_layout) on the device; a
+// set that does not fit keeps the per-group passes (mg_n stays 0).
+int mg_layout(dlsm_filterset* fs) {
+  const MGLayout M = plan_mg_layout(fs->groups, device_cus_of(fs->device));
+  if (!M.ok) return DLSM_OK;
+  DLSM_TRY(hipMalloc(reinterpret_cast<void**>(&fs->d_mg), sizeof(MGroupDev) * M.md.size()));
+  DLSM_TRY(hipMalloc(reinterpret_cast<void**>(&fs->d_mgplan), sizeof(uint32_t) * M.plan.size()));
+  DLSM_TRY(hipMemcpy(fs->d_mg, M.md.data(), sizeof(MGroupDev) * M.md.size(), hipMemcpyHostToDevice));
+  DLSM_TRY(hipMemcpy(fs->d_mgplan, M.plan.data(), sizeof(uint32_t) * M.plan.size(), hipMemcpyHostToDevice));
+  fs->mg_n = static_cast<int>(M.md.size());
+  fs->mg_slices = M.slices;
+  fs->mg_region = M.region;
+  fs->mg_abytes = M.abytes;
+  fs->mg_stage_bytes = M.stage_bytes;
+  fs->mg_classes = M.classes;
+  return DLSM_OK;
+}
+
+// The five tail bytes of a filter of len >= 5 bytes in host or device memory.
+int fetch_tail(dlsm_ctx* ctx, const uint8_t* filter, uint64_t len, bool on_device, uint8_t* tail) {
+  const uint8_t* tp = filter + len - 5;
+  if (on_device) {
+    DLSM_TRY(hipMemcpyAsync(tail, tp, 5, hipMemcpyDeviceToHost, ctx->stream));
+    DLSM_TRY(ctx_sync(ctx, ctx->stream));
+  } else {
+    memcpy(tail, tp, 5);
   }
-  if (sbase > kMGMaxSlices) return hipSuccess;
-  // every group's fixed sub-regions: entries, answers; its table columns
-  constexpr uint32_t C = kMGChunk;
-  uint32_t eoff = 0, aoff = 0;
-  for (int j = 0; j < G; j++) {
-    md[j].tcol = md[j].sbase + static_cast<uint32_t>(j);
-    md[j].eoff = eoff;
-    md[j].aoff = aoff;
-    eoff += mg_sub_entries(C, md[j].S);
-    aoff += mg_sub_abytes(C, md[j].S, md[j].lgw);
-  }
-  if (eoff > 65535u || aoff > 96u * 1024u) return hipSuccess;  // u16 table offsets / the unpermute's LDS
-  // the partition's staging LDS: the largest set of kMGSetSize groups
-  constexpr int P = kMGSetSize;
-  uint32_t stage = 0;
-  for (int j0 = 0; j0 < G; j0 += P) {
-    uint32_t st = 0;
-    for (int j = j0; j < std::min(G, j0 + P); j++) st += mg_sub_entries(C, md[j].S) * 4u;
-    stage = std::max(stage, st);
-  }
-  if (stage > 64u * 1024u) return hipSuccess;
-  const uint32_t budget = device_cus_of(fs->device);
-  std::vector<uint32_t> plan;
-  std::vector<MGClass> classes;
-  for (int j = 0; j < G;) {
-    MGClass cl;
-    cl.lgw = md[j].lgw;
-    cl.s0 = md[j].sbase;
-    cl.K = 6;
-    std::vector<double> w;  // expected entry share per slice
-    int q = j;
-    for (; q < G && md[q].lgw == cl.lgw; q++) {
-      if (md[q].k != 6) cl.K = 0;
-      for (uint32_t t = 0; t < md[q].S; t++) {
-        const uint32_t nl = std::min(md[q].R, md[q].L - t * md[q].R);
-        w.push_back(static_cast<double>(nl) / md[q].L);
-      }
-    }
-    cl.S = static_cast<uint32_t>(w.size());
-    double W = 0;
-    for (double x : w) W += x;
-    std::vector<uint32_t> parts(cl.S);
-    std::vector<std::pair<double, uint32_t>> rem;
-    uint32_t used = 0;
-    for (uint32_t t = 0; t < cl.S; t++) {
-      const double want = budget * w[t] / W;
-      parts[t] = std::max<uint32_t>(1u, static_cast<uint32_t>(want));
-      used += parts[t];
-      rem.push_back({want - parts[t], t});
-    }
-    std::sort(rem.begin(), rem.end(), [](const auto& a, const auto& b) { return a.first > b.first; });
-    for (size_t r = 0; r < rem.size() && used < budget; r++, used++) parts[rem[r].second]++;
-    cl.plan_off = static_cast<uint32_t>(plan.size());
-    uint32_t acc = 0;
-    for (uint32_t t = 0; t < cl.S; t++) {
-      plan.push_back(acc);
-      acc += parts[t];
-    }
-    plan.push_back(acc);
-    cl.wgs = acc;
-    classes.push_back(cl);
-    j = q;
-  }
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&fs->d_mg), sizeof(MGroupDev) * md.size());
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&fs->d_mgplan), sizeof(uint32_t) * plan.size());
-  if (e == hipSuccess) e = hipMemcpy(fs->d_mg, md.data(), sizeof(MGroupDev) * md.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = hipMemcpy(fs->d_mgplan, plan.data(), sizeof(uint32_t) * plan.size(), hipMemcpyHostToDevice);
-  if (e != hipSuccess) return e;
-  (void)s;
-  fs->mg_n = G;
-  fs->mg_slices = sbase;
-  fs->mg_region = eoff;
-  fs->mg_abytes = aoff;
-  fs->mg_stage_bytes = stage;
-  fs->mg_classes = classes;
-  return hipSuccess;
+  return DLSM_OK;
 }
 }  // namespace
 extern "C" {
@@ -1852,55 +1643,19 @@ struct BlocksArg {
   uint8_t* status;  // host u8 per block in the caller's order, or nullptr
 };
 
-static int filterset_create_impl(dlsm_ctx* ctx, const uint8_t* const* filters, const uint64_t* lens,
-                                 int n_filters, int filters_are_device, const BlocksArg* ba,
-                                 dlsm_filterset** out) {
-  if (!ctx || !out || !filters || !lens || n_filters < 1 || n_filters > 64) return DLSM_E_ARG;
-  *out = nullptr;
-  DeviceGuard g(ctx->device);
+// The device half of a filter-set create: fs->h holds the parsed tails (host
+// filters; sealed blocks get theirs from the ingest pass here), off each
+// filter's place in the blob.  The caller owns fs and `slots` (a pageable
+// source of a queued copy) and destroys fs on a non-zero status while both
+// are alive.
+static int filterset_upload(dlsm_ctx* ctx, const uint8_t* const* filters, const uint64_t* lens,
+                            int filters_are_device, const BlocksArg* ba, const std::vector<uint64_t>& off,
+                            bool packed, std::vector<FilterDev>& slots, dlsm_filterset* fs) {
   hipStream_t s = ctx->stream;
-  // Metadata (k, num_lines) from each filter's 5-byte tail.
-  std::vector<FilterDev> h(n_filters);
-  std::vector<uint64_t> off(n_filters);
-  uint64_t blob = 0;
-  for (int f = 0; f < n_filters && ba; f++) {
-    // sealed blocks: the device pass below reads the tails; a slot holds the
-    // whole block (host blocks are verified in place)
-    if (lens[f] && !filters[f]) return DLSM_E_ARG;
-    off[f] = blob;
-    blob += (lens[f] + 255) & ~uint64_t(255);
-  }
-  for (int f = 0; f < n_filters && !ba; f++) {
-    if (!filters[f] || lens[f] < 5) return DLSM_E_CORRUPT;
-    uint8_t tail[5];
-    const uint8_t* tp = filters[f] + lens[f] - 5;
-    if (filters_are_device) {
-      DLSM_TRY(hipMemcpyAsync(tail, tp, 5, hipMemcpyDeviceToHost, s));
-      DLSM_TRY(ctx_sync(ctx, s));
-    } else {
-      memcpy(tail, tp, 5);
-    }
-    int k, lg;
-    uint32_t L;
-    DLSM_CHECK(parse_tail(tail, lens[f], &k, &L, &lg));
-    h[f].L = L;
-    h[f].magic = fastmod_magic(L);
-    h[f].k = k;
-    h[f].lg = lg;
-    off[f] = blob;
-    blob += (lens[f] + 255) & ~uint64_t(255);
-  }
-  dlsm_filterset* fs = new (std::nothrow) dlsm_filterset();
-  if (!fs) return DLSM_E_NOMEM;
-  fs->device = ctx->device;
-  fs->F = n_filters;
-  fs->blob_bytes = blob;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&fs->blob), blob);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&fs->d_filters), sizeof(FilterDev) * n_filters);
-  if (e != hipSuccess) {
-    dlsm_filterset_destroy(fs);
-    return from_hip(e);
-  }
+  const int n_filters = fs->F;
+  std::vector<FilterDev>& h = fs->h;
+  DLSM_TRY(hipMalloc(reinterpret_cast<void**>(&fs->blob), fs->blob_bytes));
+  DLSM_TRY(hipMalloc(reinterpret_cast<void**>(&fs->d_filters), sizeof(FilterDev) * n_filters));
   if (ba) {
     // host blocks: one copy to the slot, then the pass runs in place
     std::vector<IngestBlock> blk(n_filters);
@@ -1908,86 +1663,82 @@ static int filterset_create_impl(dlsm_ctx* ctx, const uint8_t* const* filters, c
       blk[f] = IngestBlock{filters[f], fs->blob + off[f], lens[f]};
       if (filters_are_device) continue;
       blk[f].src = blk[f].dst;
-      if (lens[f]) e = hipMemcpyAsync(blk[f].dst, filters[f], lens[f], hipMemcpyHostToDevice, s);
-      if (e != hipSuccess) break;
+      if (lens[f]) DLSM_TRY(hipMemcpyAsync(blk[f].dst, filters[f], lens[f], hipMemcpyHostToDevice, s));
     }
     std::vector<IngestRecord> recs;
-    int st = e == hipSuccess ? run_ingest(ctx, blk, ba->verify, true, recs) : from_hip(e);
-    if (st == DLSM_OK) st = ingest_status(recs, {}, ba->status);
-    if (st != DLSM_OK) {
-      dlsm_filterset_destroy(fs);
-      return st;
-    }
+    DLSM_CHECK(run_ingest(ctx, blk, ba->verify, true, recs));
+    DLSM_CHECK(ingest_status(recs, {}, ba->status));
     for (int f = 0; f < n_filters; f++)
       h[f] = FilterDev{fs->blob + off[f], recs[f].L, recs[f].magic, recs[f].k, recs[f].lg};
   }
   for (int f = 0; f < n_filters && !ba; f++) {
-    e = hipMemcpyAsync(fs->blob + off[f], filters[f], lens[f],
-                       filters_are_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) break;
+    DLSM_TRY(hipMemcpyAsync(fs->blob + off[f], filters[f], lens[f],
+                            filters_are_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
     h[f].data = fs->blob + off[f];
   }
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(fs->d_filters, h.data(), sizeof(FilterDev) * n_filters, hipMemcpyHostToDevice, s);
-  fs->h = h;
-  // Sliced-probe groups: within each mask byte, the filters with one (L, k)
-  // share a stacked image.  Every filter must have 64-byte lines (the
-  // reader's common case) for the sliced path; otherwise the set is probed
-  // directly.
-  bool stack = true;
-  for (int f = 0; f < n_filters; f++) stack = stack && h[f].lg == 6;
-  std::vector<std::vector<int>> members;
-  if (stack) {
-    for (int b = 0; b * 8 < n_filters; b++) {
-      bool first = true;
-      std::vector<bool> done(8, false);
-      for (int f = 8 * b; f < std::min(n_filters, 8 * b + 8); f++) {
-        if (done[f - 8 * b]) continue;
-        ProbeGroup g;
-        g.L = h[f].L;
-        g.magic = h[f].magic;
-        g.k = h[f].k;
-        g.mask_byte = b;
-        g.first_of_byte = first;
-        first = false;
-        std::vector<int> m;
-        for (int q = f; q < std::min(n_filters, 8 * b + 8); q++)
-          if (!done[q - 8 * b] && h[q].L == g.L && h[q].k == g.k) {
-            done[q - 8 * b] = true;
-            m.push_back(q);
-          }
-        const int nm = static_cast<int>(m.size());
-        g.lgw = nm == 1 ? 0 : nm == 2 ? 1 : nm <= 4 ? 2 : 3;
-        if (const char* e = getenv("DLSM_PROBE_PACKED"); e && atoi(e) == 0) g.lgw = 3;  // A/B knob
-        for (int j = 0; j < nm && g.lgw < 3; j++) g.slotmap |= static_cast<uint32_t>(m[j] % 8) << (4 * j);
-        fs->groups.push_back(g);
-        members.push_back(m);
-      }
-    }
-  }
+  DLSM_TRY(hipMemcpyAsync(fs->d_filters, h.data(), sizeof(FilterDev) * n_filters, hipMemcpyHostToDevice, s));
+  const FilterGroupPlan gp = plan_filter_groups(h, packed);
+  fs->groups = gp.groups;
   const size_t G = fs->groups.size();
-  if (e == hipSuccess && G) {
-    std::vector<FilterDev> slots(8 * G, FilterDev{nullptr, 0, 0, 0, 0});
+  if (G) {
+    slots.assign(8 * G, FilterDev{nullptr, 0, 0, 0, 0});
     for (size_t g = 0; g < G; g++)
-      for (int f : members[g]) slots[8 * g + (f % 8)] = h[f];
-    e = hipMalloc(reinterpret_cast<void**>(&fs->d_slots), sizeof(FilterDev) * slots.size());
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(fs->d_slots, slots.data(), sizeof(FilterDev) * slots.size(), hipMemcpyHostToDevice, s);
-    for (size_t g = 0; g < G && e == hipSuccess; g++) {
+      for (int f : gp.members[g]) slots[8 * g + (f % 8)] = h[f];
+    DLSM_TRY(hipMalloc(reinterpret_cast<void**>(&fs->d_slots), sizeof(FilterDev) * slots.size()));
+    DLSM_TRY(hipMemcpyAsync(fs->d_slots, slots.data(), sizeof(FilterDev) * slots.size(), hipMemcpyHostToDevice, s));
+    for (size_t g = 0; g < G; g++) {
       ProbeGroup& grp = fs->groups[g];
       const uint64_t bytes = static_cast<uint64_t>(grp.L) * (64u << grp.lgw);
-      e = hipMalloc(reinterpret_cast<void**>(&grp.stacked), bytes);
-      if (e == hipSuccess)
-        e = grp.lgw == 3 ? launch_stack_filters(fs->d_slots + 8 * g, grp.L, grp.stacked, s)
-                         : launch_pack_filters(fs->d_slots + 8 * g, grp.slotmap, grp.lgw, grp.L, grp.stacked, s);
+      DLSM_TRY(hipMalloc(reinterpret_cast<void**>(&grp.stacked), bytes));
+      DLSM_TRY(grp.lgw == 3 ? launch_stack_filters(fs->d_slots + 8 * g, grp.L, grp.stacked, s)
+                            : launch_pack_filters(fs->d_slots + 8 * g, grp.slotmap, grp.lgw, grp.L, grp.stacked, s));
       fs->stacked_bytes += bytes;
     }
   }
-  if (e == hipSuccess && G >= 2 && G <= static_cast<size_t>(kMGMaxGroups)) e = mg_layout(fs, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);  // `slots` (and mg_layout's tables) are pageable host memory
-  if (e != hipSuccess) {
+  if (G >= 2 && G <= static_cast<size_t>(kMGMaxGroups)) DLSM_CHECK(mg_layout(fs));
+  DLSM_TRY(hipStreamSynchronize(s));  // `slots` and fs->h are pageable host memory
+  return DLSM_OK;
+}
+
+static int filterset_create_impl(dlsm_ctx* ctx, const uint8_t* const* filters, const uint64_t* lens,
+                                 int n_filters, int filters_are_device, const BlocksArg* ba,
+                                 dlsm_filterset** out) {
+  if (!ctx || !out || !filters || !lens || n_filters < 1 || n_filters > 64) return DLSM_E_ARG;
+  *out = nullptr;
+  DeviceGuard g(ctx->device);
+  // Metadata (k, num_lines) from each filter's 5-byte tail.
+  std::vector<FilterDev> h(n_filters);
+  std::vector<uint64_t> off(n_filters);
+  uint64_t blob = 0;
+  for (int f = 0; f < n_filters; f++) {
+    if (ba) {
+      // sealed blocks: the device pass reads the tails; a slot holds the
+      // whole block (host blocks are verified in place)
+      if (lens[f] && !filters[f]) return DLSM_E_ARG;
+    } else {
+      if (!filters[f] || lens[f] < 5) return DLSM_E_CORRUPT;
+      uint8_t tail[5];
+      DLSM_CHECK(fetch_tail(ctx, filters[f], lens[f], filters_are_device, tail));
+      int k, lg;
+      uint32_t L;
+      DLSM_CHECK(parse_tail(tail, lens[f], &k, &L, &lg));
+      h[f] = FilterDev{nullptr, L, fastmod_magic(L), k, lg};
+    }
+    off[f] = blob;
+    blob += (lens[f] + 255) & ~uint64_t(255);
+  }
+  const char* pk = getenv("DLSM_PROBE_PACKED");  // A/B knob: 0 = byte-wide images only
+  dlsm_filterset* fs = new (std::nothrow) dlsm_filterset();
+  if (!fs) return DLSM_E_NOMEM;
+  fs->device = ctx->device;
+  fs->F = n_filters;
+  fs->blob_bytes = blob;
+  fs->h = h;
+  std::vector<FilterDev> slots;
+  const int st = filterset_upload(ctx, filters, lens, filters_are_device, ba, off, !(pk && atoi(pk) == 0), slots, fs);
+  if (st != DLSM_OK) {
     dlsm_filterset_destroy(fs);
-    return from_hip(e);
+    return st;
   }
   *out = fs;
   return DLSM_OK;
@@ -2028,48 +1779,6 @@ int dlsm_filterset_size(const dlsm_filterset* fs, int* n_filters, uint64_t* devi
 
 namespace {
 
-// Slices of a group's image (line count L): the LDS holds up to 2^lgR lines
-// (a byte-wide stacked table with more than kMaxSlices slices of 64 KiB moves
-// to 128 KiB, one workgroup per CU; packed images always use 128 KiB of
-// 2^(11 - lgw) lines).  Balanced: the slice pass runs S x parts workgroups
-// with parts = 256 / S0 (slice_parts, S0 = the slice count at full width),
-// so the slices are narrowed to R = ceil(L / floor(256 / parts)) lines to fill
-// the 256 CUs exactly -- 8 x 1.6 M-key filters (31,251 lines): 128 slices of
-// 245 lines x 2 parts = 256 workgroups instead of 123 x 2 = 246.
-// Returns S, or 0 when the group cannot be sliced.
-uint32_t group_slices(const dlsm_ctx* ctx, const ProbeGroup& g, int* lgR, uint32_t* R_out) {
-  const uint32_t L = g.L;
-  if (g.lgw < 3) {
-    *lgR = 11 - g.lgw;
-  } else {
-    *lgR = ctx->probe_lgr;
-    if (ceil_div_u32(L, 1u << *lgR) > kMaxSlices && *lgR < 8) *lgR = 8;
-  }
-  const uint32_t Rmax = 1u << *lgR;
-  const uint32_t S0 = ceil_div_u32(L, Rmax);
-  if (S0 < 1 || S0 > kMaxSlices) return 0;
-  uint32_t R = Rmax;
-  const uint32_t per_cu = *lgR == 7 && g.lgw == 3 ? 2u : 1u;  // slice workgroups resident per CU
-  const uint32_t slots = kBuildSliceCUs * per_cu;
-  if (S0 < slots) {
-    const uint32_t parts = std::max(1u, slots / S0);
-    const uint32_t S_target = slots / parts;
-    R = std::min(Rmax, ceil_div_u32(L, S_target));
-  }
-  *R_out = R;
-  return ceil_div_u32(L, R);
-}
-
-// (slice, part) workgroups of the slice pass: about one resident wave of
-// workgroups (256 CUs x 2 slices of 64 KiB or 1 of 128 KiB), each part at
-// least one chunk per wave (a part's waves split its chunks into equal
-// groups).
-int slice_parts(uint32_t S, uint32_t nC, int lgR) {
-  const uint32_t resident = 256u * (lgR == 7 ? 2u : 1u);
-  int parts = static_cast<int>(std::max<uint32_t>(1, (resident + S / 2) / S));
-  return std::min<int>(parts, static_cast<int>(std::max<uint32_t>(1, nC / 16)));
-}
-
 // A filter set of several groups (filters of different sizes, more than 8
 // filters): every lookup is hashed ONCE (hash pass, 4 B per key), then each
 // group partitions the hashes by its own line count and probes its stacked
@@ -2096,7 +1805,7 @@ int probe_grouped(dlsm_ctx* ctx, const dlsm_filterset* fs, const KeyDesc& kd, in
   for (const auto& g : fs->groups) {
     int lg;
     uint32_t R;
-    Smax = std::max(Smax, group_slices(ctx, g, &lg, &R));
+    Smax = std::max(Smax, group_slices(ctx->probe_lgr, g.L, g.lgw, &lg, &R));
   }
   const uint64_t rstride = static_cast<uint64_t>(nC) * probe_region(static_cast<uint32_t>(C));
   DLSM_CHECK(ctx->entries.ensure(rstride));
@@ -2107,7 +1816,7 @@ int probe_grouped(dlsm_ctx* ctx, const dlsm_filterset* fs, const KeyDesc& kd, in
     const ProbeGroup& g = fs->groups[gi];
     int lgR;
     uint32_t R;
-    const uint32_t S = group_slices(ctx, g, &lgR, &R);
+    const uint32_t S = group_slices(ctx->probe_lgr, g.L, g.lgw, &lgR, &R);
     if (S == 0 || ctx->path == 1) {
       DLSM_TRY(launch_probe_direct_group(fs->d_slots + 8 * gi, hk, mask_dev, mb, g.mask_byte,
                                          g.first_of_byte, s));
@@ -2143,12 +1852,10 @@ int probe_multi(dlsm_ctx* ctx, const dlsm_filterset* fs, const KeyDesc& kd, int 
   // two streams as in the one-group path: round r's partition (HBM-bound, on
   // the helper stream) beside round r-1's slice pass (LDS-bound) and
   // unpermute, over kProbeBufs rotating buffer sets.
-  uint64_t round = n;
-  if (ctx->probe_round && ctx->probe_round < n) round = std::max<uint64_t>(C, (ctx->probe_round / C) * C);
-  const uint64_t n_rounds = (n + round - 1) / round;
-  const bool pipe = n_rounds > 1 && !ctx->probe_serial;
-  const int nbuf = pipe ? kProbeBufs : 1;
-  const uint64_t nCmax = (std::min(round, n) + C - 1) >> lgC;
+  const ProbeRounds pr = probe_rounds(n, ctx->probe_round, ctx->probe_serial, C);
+  const uint64_t round = pr.round, n_rounds = pr.n_rounds, nCmax = pr.nCmax;
+  const bool pipe = pr.pipe;
+  const int nbuf = pr.nbuf;
   const uint64_t estride = nCmax * fs->mg_region, astride = nCmax * fs->mg_abytes;
   const uint64_t pstride = nCmax * G * C, tstride = nCmax * rowlen;
   DLSM_CHECK(ctx->entries.ensure(estride * nbuf));
@@ -2166,10 +1873,7 @@ int probe_multi(dlsm_ctx* ctx, const dlsm_filterset* fs, const KeyDesc& kd, int 
     uint8_t* ans = ctx->smask.p + b * astride;
     uint16_t* pos = ctx->pos.p + b * pstride;
     uint16_t* tab = ctx->tab.p + b * tstride;
-    KeyDesc kr = kd;
-    kr.n = nr;
-    if (kd.offsets) kr.offsets = kd.offsets + r0;
-    else kr.bytes = kd.bytes + r0 * kd.key_len;
+    const KeyDesc kr = round_keys(kd, r0, nr);
     if (pipe && r >= static_cast<uint64_t>(nbuf)) DLSM_TRY(hipStreamWaitEvent(ps, ctx->ev_free[b], 0));
     DLSM_TRY(launch_probe_mpartition(kr, fs->d_mg, G, rowlen, fs->mg_region, fs->mg_stage_bytes, ent, pos, tab,
                                      mode, ps));
@@ -2209,7 +1913,7 @@ int full_probe_dev_impl(dlsm_ctx* ctx, const dlsm_filterset* fs, const dlsm_keys
   for (const auto& grp : fs->groups) {
     int lg;
     uint32_t R;
-    all_sliceable = all_sliceable && group_slices(ctx, grp, &lg, &R) != 0;
+    all_sliceable = all_sliceable && group_slices(ctx->probe_lgr, grp.L, grp.lgw, &lg, &R) != 0;
   }
   if (ctx->path == 2 && !(all_sliceable && fits)) return DLSM_E_ARG;
   if (fs->groups.empty() || ctx->path == 1 || !fits) {
@@ -2225,7 +1929,7 @@ int full_probe_dev_impl(dlsm_ctx* ctx, const dlsm_filterset* fs, const dlsm_keys
   const ProbeGroup& grp = fs->groups[0];
   int lgR;
   uint32_t R;
-  const uint32_t S = group_slices(ctx, grp, &lgR, &R);
+  const uint32_t S = group_slices(ctx->probe_lgr, grp.L, grp.lgw, &lgR, &R);
   // Rounds of probe_round keys, pipelined: round r's partition (helper
   // stream) overlaps round r-1's slice + unpermute (context stream), or
   // serial (DLSM_OPT_PROBE_ROUND_SERIAL).  A round's intermediates (4 B hash +
@@ -2233,13 +1937,10 @@ int full_probe_dev_impl(dlsm_ctx* ctx, const dlsm_filterset* fs, const dlsm_keys
   // buffers, small enough to stay resident in the 256 MiB Infinity Cache
   // while the keys stream past.
   const uint64_t n = keys->n;
-  uint64_t round = n;
-  if (ctx->probe_round && ctx->probe_round < n)
-    round = std::max<uint64_t>(C, (ctx->probe_round / C) * C);
-  const uint64_t n_rounds = (n + round - 1) / round;
-  const bool pipe = n_rounds > 1 && !ctx->probe_serial;
-  const int nbuf = pipe ? kProbeBufs : 1;
-  const uint32_t nCmax = ceil_div_u32(std::min(round, n), C);
+  const ProbeRounds pr = probe_rounds(n, ctx->probe_round, ctx->probe_serial, C);
+  const uint64_t round = pr.round, n_rounds = pr.n_rounds, nCmax = pr.nCmax;
+  const bool pipe = pr.pipe;
+  const int nbuf = pr.nbuf;
   const uint64_t kstride = static_cast<uint64_t>(nCmax) * C;  // keys per buffer (16-B aligned)
   const uint64_t rstride = static_cast<uint64_t>(nCmax) * probe_region(static_cast<uint32_t>(C));  // entries / answers
   const uint64_t tstride = static_cast<uint64_t>(S + 1) * nCmax;        // table u16 per buffer
@@ -2262,10 +1963,7 @@ int full_probe_dev_impl(dlsm_ctx* ctx, const dlsm_filterset* fs, const dlsm_keys
     uint16_t* pos = ctx->pos.p + b * kstride;
     uint8_t* sm = ctx->smask.p + b * rstride;
     uint16_t* tab = ctx->tab.p + b * tstride;
-    KeyDesc kr = kd;
-    kr.n = nr;
-    if (kd.offsets) kr.offsets = kd.offsets + r0;
-    else kr.bytes = kd.bytes + r0 * kd.key_len;
+    const KeyDesc kr = round_keys(kd, r0, nr);
     if (pipe && r >= static_cast<uint64_t>(nbuf)) DLSM_TRY(hipStreamWaitEvent(ps, ctx->ev_free[b], 0));
     DLSM_TRY(launch_probe_partition(kr, grp.L, grp.magic, R, S, ent, pos, tab, mode, lgC, ps,
                                     split ? ctx->pcus : 0u));
@@ -2312,47 +2010,6 @@ int dlsm_bloom_full_probe(dlsm_ctx* ctx, const dlsm_filterset* fs, const dlsm_ke
 // ---------------------------------------------------------------------------
 // Legacy block-based filter block (table/filter_block.cc), §8f row 4
 // ---------------------------------------------------------------------------
-namespace {
-constexpr uint64_t kFilterBaseLg = 11;  // filter_block.cc:15-16: a filter every 2 KiB
-
-// FilterBlockBuilder's filter groups for the StartBlock / AddKey sequence of a
-// TableBuilder: keys of data block b, then StartBlock(block_end_offset[b])
-// (TableBuilder::Flush); GenerateFilter takes every pending key (first loop
-// turn) or none (later turns); Finish generates one more if keys are pending.
-struct FilterGroups {
-  std::vector<uint64_t> begin, end;  // key range per filter (empty allowed)
-  std::vector<uint32_t> off;         // filter_offsets_
-  uint64_t array_offset = 0;
-  uint64_t total = 0;  // block length
-};
-
-int filter_groups(const uint64_t* block_key_end, const uint64_t* block_end_offset, int n_blocks,
-                  uint64_t n_keys, int bits_per_key, FilterGroups& G) {
-  if (n_blocks < 0 || (n_blocks > 0 && (!block_key_end || !block_end_offset))) return DLSM_E_ARG;
-  uint64_t pending = 0, prev_end = 0, result = 0;
-  auto generate = [&](uint64_t upto) {
-    G.off.push_back(static_cast<uint32_t>(result));
-    G.begin.push_back(pending);
-    G.end.push_back(upto);
-    if (upto > pending) result += legacy_bits(upto - pending, bits_per_key) / 8 + 1;  // CreateFilter
-    pending = upto;
-  };
-  for (int b = 0; b < n_blocks; b++) {
-    const uint64_t ke = block_key_end[b];
-    if (ke < prev_end || ke > n_keys) return DLSM_E_ARG;
-    prev_end = ke;
-    const uint64_t index = block_end_offset[b] / (uint64_t(1) << kFilterBaseLg);
-    if (index < G.off.size()) return DLSM_E_ARG;  // assert(filter_index >= filter_offsets_.size())
-    while (index > G.off.size()) generate(ke);     // later turns: no pending keys -> empty
-  }
-  if (n_keys > pending) generate(n_keys);  // Finish: start_ not empty
-  G.array_offset = result;
-  G.total = result + 4 * G.off.size() + 4 + 1;
-  if (G.array_offset > 0xffffffffull) return DLSM_E_ARG;  // Fixed32 offsets
-  return DLSM_OK;
-}
-}  // namespace
-
 int dlsm_filter_block_size(const uint64_t* block_key_end, const uint64_t* block_end_offset,
                            int n_blocks, uint64_t n_keys, int bits_per_key, uint64_t* nbytes) {
   if (!nbytes) return DLSM_E_ARG;
@@ -2468,15 +2125,6 @@ int dlsm_filter_block_probe(dlsm_ctx* ctx, const uint8_t* block, uint64_t len, c
 // ---------------------------------------------------------------------------
 static_assert(DLSM_NUM_LEVELS == kNumLevels, "config::kNumLevels");
 
-// A level probed by the sliced version probe: its filters' lines back to
-// back in one image (`image`, `lines` lines of 64 B, one probe count `k`).
-struct VersionLevel {
-  int level = 0;
-  int k = 0;
-  uint32_t lines = 0;
-  const uint8_t* image = nullptr;
-};
-
 struct dlsm_version {
   int device = 0;
   VersionDev v{};
@@ -2508,265 +2156,106 @@ uint64_t version_slice_min_bytes() {
 }
 }  // namespace
 
-static int version_create_impl(dlsm_ctx* ctx, const dlsm_version_file* files, int n_files,
-                               int filters_are_device, const BlocksArg* ba, dlsm_version** out) {
-  if (!ctx || !out || n_files < 0 || (n_files > 0 && !files)) return DLSM_E_ARG;
-  *out = nullptr;
-  DeviceGuard g(ctx->device);
+// The device half of a version create: allocate, (sealed blocks: ingest,)
+// copy the filters and the plan's tables.  The caller owns the plan and h
+// (the plan's file table, here given its device pointers) -- pageable sources
+// of queued copies -- and ver, and destroys ver on a non-zero status while
+// they are alive.
+static int version_upload(dlsm_ctx* ctx, const VersionPlan& P, const dlsm_version_file* files,
+                          int filters_are_device, const BlocksArg* ba, std::vector<VFileDev>& h, dlsm_version* ver) {
   hipStream_t s = ctx->stream;
-  // search order: level 0 newest first (NewestFirst, version_set.cc:268-270),
-  // then each level >= 1 in the caller's (key) order
-  std::vector<int> order;
-  int n_l0 = 0;
-  uint32_t begin[kNumLevels] = {}, count[kNumLevels] = {};
-  for (int f = 0; f < n_files; f++) {
-    const dlsm_version_file& F = files[f];
-    if (F.level < 0 || F.level >= kNumLevels) return DLSM_E_ARG;
-    if ((F.smallest_len && !F.smallest_user_key) || (F.largest_len && !F.largest_user_key)) return DLSM_E_ARG;
-    if (F.smallest_len > 0xffffffffull || F.largest_len > 0xffffffffull) return DLSM_E_ARG;
-    if (F.level == 0) n_l0++;
-  }
-  if (n_l0 > 64 - (kNumLevels - 1)) return DLSM_E_ARG;
-  for (int f = 0; f < n_files; f++)
-    if (files[f].level == 0) order.push_back(f);
-  std::stable_sort(order.begin(), order.end(),
-                   [&](int a, int b) { return files[a].number > files[b].number; });
-  for (int lv = 1; lv < kNumLevels; lv++) {
-    begin[lv] = static_cast<uint32_t>(order.size());
-    for (int f = 0; f < n_files; f++)
-      if (files[f].level == lv) order.push_back(f);
-    count[lv] = static_cast<uint32_t>(order.size()) - begin[lv];
-  }
-  // layout: VFileDev[n] | key blob | filters (each 256-B aligned)
-  std::vector<VFileDev> h(n_files);
-  std::vector<uint8_t> keys;
-  std::vector<uint64_t> foff(n_files, 0);
-  const uint64_t files_bytes = (sizeof(VFileDev) * n_files + 255) & ~uint64_t(255);
-  for (int j = 0; j < n_files; j++) {
-    const dlsm_version_file& F = files[order[j]];
-    VFileDev& d = h[j];
-    d.smallest_off = keys.size();
-    d.smallest_len = static_cast<uint32_t>(F.smallest_len);
-    keys.insert(keys.end(), F.smallest_user_key, F.smallest_user_key + F.smallest_len);
-    d.largest_off = keys.size();
-    d.largest_len = static_cast<uint32_t>(F.largest_len);
-    keys.insert(keys.end(), F.largest_user_key, F.largest_user_key + F.largest_len);
-    d.largest_trailer = F.largest_trailer;
-    d.f = FilterDev{};
-  }
-  // 16-byte big-endian key prefixes (VersionDev::pre_small / pre_large)
-  std::vector<ulonglong2> pre(2 * static_cast<size_t>(n_files));
-  auto be_prefix = [](const uint8_t* p, uint64_t n) {
-    ulonglong2 r{0, 0};
-    for (uint64_t i = 0; i < 16 && i < n; i++) {
-      if (i < 8) r.x |= static_cast<uint64_t>(p[i]) << (56 - 8 * i);
-      else r.y |= static_cast<uint64_t>(p[i]) << (56 - 8 * (i - 8));
-    }
-    return r;
-  };
-  for (int j = 0; j < n_files; j++) {
-    pre[j] = be_prefix(keys.data() + h[j].smallest_off, h[j].smallest_len);
-    pre[n_files + j] = be_prefix(keys.data() + h[j].largest_off, h[j].largest_len);
-  }
-  const uint64_t pre_bytes = (sizeof(ulonglong2) * pre.size() + 255) & ~uint64_t(255);
-  const uint64_t keys_bytes = (keys.size() + 255) & ~uint64_t(255);
-  // The interval index (VIntervalDev): the distinct bound prefixes in order,
-  // and per open interval between two of them the level-0 files that hold
-  // it and each level's FindFile pick.  For a lookup prefix strictly between
-  // bnd[j-1] and bnd[j]: a bound with prefix index < j sorts below the lookup,
-  // one with index >= j above it.
-  auto pre_lt = [](const ulonglong2& a, const ulonglong2& b) { return a.x < b.x || (a.x == b.x && a.y < b.y); };
-  std::vector<ulonglong2> bnd(pre);
-  std::sort(bnd.begin(), bnd.end(), pre_lt);
-  bnd.erase(std::unique(bnd.begin(), bnd.end(),
-                        [](const ulonglong2& a, const ulonglong2& b) { return a.x == b.x && a.y == b.y; }),
-            bnd.end());
-  auto bidx = [&](const ulonglong2& p) {
-    return static_cast<uint32_t>(std::lower_bound(bnd.begin(), bnd.end(), p, pre_lt) - bnd.begin());
-  };
-  std::vector<uint32_t> is(n_files), il(n_files);
-  for (int j = 0; j < n_files; j++) {
-    is[j] = bidx(pre[j]);
-    il[j] = bidx(pre[n_files + j]);
-  }
-  const uint32_t n_bnd = static_cast<uint32_t>(bnd.size());
-  std::vector<VIntervalDev> ivl(n_bnd + 1);
-  // FindFile's pick per level as a two-pointer sweep: right(j) = the first
-  // file r < count-1 whose largest has prefix index >= j (else count-1); the
-  // set of such r only shrinks as j grows, so right(j) never decreases and
-  // each level is walked once over all j (O(n_bnd + files), not O(n_bnd x
-  // files): a 60,000-file level took seconds per version before).
-  uint32_t rgt[kNumLevels] = {};
-  for (uint32_t j = 0; j <= n_bnd; j++) {
-    VIntervalDev& r = ivl[j];
-    r.l0mask = 0;
-    r.reserved[0] = r.reserved[1] = r.reserved[2] = 0;
-    for (int f = 0; f < n_l0; f++)  // smallest <= lookup <= largest
-      if (is[f] < j && il[f] >= j) r.l0mask |= 1ull << f;
-    for (int lv = 1; lv < kNumLevels; lv++) {
-      r.pick[lv - 1] = 0xffffu;
-      if (!count[lv] || begin[lv] + count[lv] > 0xffffu) continue;  // (> 65,535 files: never read)
-      // FindFile (version_set.cc:95-118): files [0, count-1) whose largest
-      // sorts below the lookup come first; right starts at count-1
-      uint32_t& right = rgt[lv];
-      while (right < count[lv] - 1 && il[begin[lv] + right] < j) right++;
-      if (is[begin[lv] + right] < j) r.pick[lv - 1] = static_cast<uint16_t>(begin[lv] + right);
-    }
-  }
-  const uint64_t bnd_bytes = (sizeof(ulonglong2) * std::max<size_t>(1, bnd.size()) + 255) & ~uint64_t(255);
-  const uint64_t ivl_bytes = (sizeof(VIntervalDev) * ivl.size() + 255) & ~uint64_t(255);
-  uint64_t total = files_bytes + pre_bytes + keys_bytes + bnd_bytes + ivl_bytes;
-  for (int j = 0; j < n_files; j++) {
-    const dlsm_version_file& F = files[order[j]];
-    if (!F.filter || ba) continue;  // sealed blocks: the device pass reads the tails
-    if (F.filter_len < 5) return DLSM_E_CORRUPT;
-    uint8_t tail[5];
-    if (filters_are_device) {
-      DLSM_TRY(hipMemcpyAsync(tail, F.filter + F.filter_len - 5, 5, hipMemcpyDeviceToHost, s));
-      DLSM_TRY(ctx_sync(ctx, s));
-    } else {
-      memcpy(tail, F.filter + F.filter_len - 5, 5);
-    }
-    int k, lg;
-    uint32_t L;
-    DLSM_CHECK(parse_tail(tail, F.filter_len, &k, &L, &lg));
-    h[j].f.L = L;
-    h[j].f.magic = fastmod_magic(L);
-    h[j].f.k = k;
-    h[j].f.lg = lg;
-  }
-  // Levels for the sliced probe; their filters' lines are laid out back to
-  // back (line0 per file), the other filters one by one, 256-byte aligned.
-  std::vector<VersionLevel> sliced;
-  int32_t lvl_sliced[kNumLevels];
-  std::vector<uint64_t> copy_len(n_files, 0);
-  for (int lv = 0; lv < kNumLevels; lv++) lvl_sliced[lv] = -1;
-  // (from sealed blocks the line counts are not known before the layout: no level is sliced)
-  const uint64_t min_bytes = ba ? 0
-                             : ctx->vslice_bytes == 0 ? version_slice_min_bytes()
-                             : (ctx->vslice_bytes == UINT64_MAX ? 0 : ctx->vslice_bytes);
-  for (int lv = 1; lv < kNumLevels && min_bytes; lv++) {
-    uint64_t lines = 0;
-    int k = 0;
-    bool ok = true;
-    for (uint32_t j = begin[lv]; j < begin[lv] + count[lv]; j++) {
-      if (!files[order[j]].filter) continue;
-      ok = ok && h[j].f.lg == 6 && (k == 0 || h[j].f.k == k);
-      k = h[j].f.k;
-      lines += h[j].f.L;
-    }
-    if (!ok || lines * 64 <= min_bytes || lines >= kVNoLine) continue;
-    lvl_sliced[lv] = static_cast<int32_t>(sliced.size());
-    VersionLevel vl;
-    vl.level = lv;
-    vl.k = k;
-    vl.lines = static_cast<uint32_t>(lines);
-    sliced.push_back(vl);
-  }
-  std::vector<uint64_t> image_off(sliced.size(), 0);
-  for (size_t q = 0; q < sliced.size(); q++) {
-    const int lv = sliced[q].level;
-    image_off[q] = total;
-    uint32_t line0 = 0;
-    for (uint32_t j = begin[lv]; j < begin[lv] + count[lv]; j++) {
-      if (!files[order[j]].filter) continue;
-      h[j].line0 = line0;
-      foff[j] = total + static_cast<uint64_t>(line0) * 64;
-      copy_len[j] = static_cast<uint64_t>(h[j].f.L) * 64;  // the lines; the trailer was parsed above
-      line0 += h[j].f.L;
-    }
-    total += (static_cast<uint64_t>(sliced[q].lines) * 64 + 255) & ~uint64_t(255);
-  }
-  for (int j = 0; j < n_files; j++) {
-    const dlsm_version_file& F = files[order[j]];
-    if (!F.filter || copy_len[j]) continue;
-    foff[j] = total;
-    copy_len[j] = F.filter_len;
-    total += (F.filter_len + 255) & ~uint64_t(255);
-  }
-  dlsm_version* ver = new (std::nothrow) dlsm_version();
-  if (!ver) return DLSM_E_NOMEM;
-  ver->device = ctx->device;
-  ver->n_files = n_files;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&ver->mem), std::max<uint64_t>(total, 256));
-  if (ba && e == hipSuccess) {
+  const int n_files = ver->n_files;
+  h = P.h;
+  DLSM_TRY(hipMalloc(reinterpret_cast<void**>(&ver->mem), std::max<uint64_t>(P.total, 256)));
+  if (ba) {
     // one verify-and-ingest pass over every file's block (search order);
     // host blocks are copied to their slots first and verified in place
     std::vector<IngestBlock> blk;
     std::vector<int> where, slot;
-    for (int j = 0; j < n_files && e == hipSuccess; j++) {
-      const dlsm_version_file& F = files[order[j]];
-      if (ba->status) ba->status[order[j]] = DLSM_BLOCK_OK;
+    for (int j = 0; j < n_files; j++) {
+      const dlsm_version_file& F = files[P.order[j]];
+      if (ba->status) ba->status[P.order[j]] = DLSM_BLOCK_OK;
       if (!F.filter) continue;
-      IngestBlock b{F.filter, ver->mem + foff[j], F.filter_len};
+      IngestBlock b{F.filter, ver->mem + P.foff[j], F.filter_len};
       if (!filters_are_device) {
         b.src = b.dst;
-        if (F.filter_len) e = hipMemcpyAsync(b.dst, F.filter, F.filter_len, hipMemcpyHostToDevice, s);
+        if (F.filter_len) DLSM_TRY(hipMemcpyAsync(b.dst, F.filter, F.filter_len, hipMemcpyHostToDevice, s));
       }
       blk.push_back(b);
-      where.push_back(order[j]);
+      where.push_back(P.order[j]);
       slot.push_back(j);
     }
     std::vector<IngestRecord> recs;
-    int st = e == hipSuccess ? run_ingest(ctx, blk, ba->verify, true, recs) : from_hip(e);
-    if (st == DLSM_OK) st = ingest_status(recs, where, ba->status);
-    if (st != DLSM_OK) {
-      dlsm_version_destroy(ver);
-      return st;
-    }
+    DLSM_CHECK(run_ingest(ctx, blk, ba->verify, true, recs));
+    DLSM_CHECK(ingest_status(recs, where, ba->status));
     for (size_t q = 0; q < blk.size(); q++)
       h[slot[q]].f = FilterDev{blk[q].dst, recs[q].L, recs[q].magic, recs[q].k, recs[q].lg};
   }
-  for (int j = 0; j < n_files && e == hipSuccess && !ba; j++) {
-    const dlsm_version_file& F = files[order[j]];
+  for (int j = 0; j < n_files && !ba; j++) {
+    const dlsm_version_file& F = files[P.order[j]];
     if (!F.filter) continue;
-    h[j].f.data = ver->mem + foff[j];
-    e = hipMemcpyAsync(ver->mem + foff[j], F.filter, copy_len[j],
-                       filters_are_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
+    h[j].f.data = ver->mem + P.foff[j];
+    DLSM_TRY(hipMemcpyAsync(ver->mem + P.foff[j], F.filter, P.copy_len[j],
+                            filters_are_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
   }
-  for (size_t q = 0; q < sliced.size(); q++) sliced[q].image = ver->mem + image_off[q];
-  ver->sliced = sliced;
-  if (e == hipSuccess && n_files)
-    e = hipMemcpyAsync(ver->mem, h.data(), sizeof(VFileDev) * n_files, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && n_files)
-    e = hipMemcpyAsync(ver->mem + files_bytes, pre.data(), sizeof(ulonglong2) * pre.size(),
-                       hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && !keys.empty())
-    e = hipMemcpyAsync(ver->mem + files_bytes + pre_bytes, keys.data(), keys.size(), hipMemcpyHostToDevice, s);
-  const uint64_t bnd_off = files_bytes + pre_bytes + keys_bytes;
-  if (e == hipSuccess && !bnd.empty())
-    e = hipMemcpyAsync(ver->mem + bnd_off, bnd.data(), sizeof(ulonglong2) * bnd.size(), hipMemcpyHostToDevice, s);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(ver->mem + bnd_off + bnd_bytes, ivl.data(), sizeof(VIntervalDev) * ivl.size(),
-                       hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);  // pageable sources: finish before returning
-  if (e != hipSuccess) {
-    dlsm_version_destroy(ver);
-    return from_hip(e);
+  ver->sliced = P.sliced;
+  for (size_t q = 0; q < ver->sliced.size(); q++) ver->sliced[q].image = ver->mem + P.image_off[q];
+  const uint64_t pre_off = P.files_bytes, keys_off = pre_off + P.pre_bytes;
+  const uint64_t bnd_off = keys_off + P.keys_bytes, ivl_off = bnd_off + P.bnd_bytes;
+  if (n_files) {
+    DLSM_TRY(hipMemcpyAsync(ver->mem, h.data(), sizeof(VFileDev) * n_files, hipMemcpyHostToDevice, s));
+    DLSM_TRY(hipMemcpyAsync(ver->mem + pre_off, P.pre.data(), sizeof(ulonglong2) * P.pre.size(),
+                            hipMemcpyHostToDevice, s));
   }
+  if (!P.keys.empty())
+    DLSM_TRY(hipMemcpyAsync(ver->mem + keys_off, P.keys.data(), P.keys.size(), hipMemcpyHostToDevice, s));
+  if (!P.bnd.empty())
+    DLSM_TRY(hipMemcpyAsync(ver->mem + bnd_off, P.bnd.data(), sizeof(ulonglong2) * P.bnd.size(),
+                            hipMemcpyHostToDevice, s));
+  DLSM_TRY(hipMemcpyAsync(ver->mem + ivl_off, P.ivl.data(), sizeof(VIntervalDev) * P.ivl.size(),
+                          hipMemcpyHostToDevice, s));
+  DLSM_TRY(hipStreamSynchronize(s));  // pageable sources: finish before returning
   ver->v.files = reinterpret_cast<const VFileDev*>(ver->mem);
-  ver->v.pre_small = reinterpret_cast<const ulonglong2*>(ver->mem + files_bytes);
+  ver->v.pre_small = reinterpret_cast<const ulonglong2*>(ver->mem + pre_off);
   ver->v.pre_large = ver->v.pre_small + n_files;
-  ver->v.keyblob = ver->mem + files_bytes + pre_bytes;
+  ver->v.keyblob = ver->mem + keys_off;
   ver->v.bnd = reinterpret_cast<const ulonglong2*>(ver->mem + bnd_off);
-  ver->v.ivl = reinterpret_cast<const VIntervalDev*>(ver->mem + bnd_off + bnd_bytes);
-  ver->v.n_bnd = n_bnd;
-  ver->v.k_all = 0;
-  {
-    int kc = 0;
-    bool same = true;
-    for (int j = 0; j < n_files; j++) {
-      if (!files[order[j]].filter) continue;
-      same = same && (kc == 0 || h[j].f.k == kc);
-      kc = h[j].f.k;
-    }
-    ver->v.k_all = same ? kc : 0;
-  }
-  ver->v.n_l0 = static_cast<uint32_t>(n_l0);
+  ver->v.ivl = reinterpret_cast<const VIntervalDev*>(ver->mem + ivl_off);
+  ver->v.n_bnd = static_cast<uint32_t>(P.bnd.size());
+  ver->v.k_all = ba ? version_k_all(files, P.order, h) : P.k_all;
+  ver->v.n_l0 = static_cast<uint32_t>(P.n_l0);
   for (int lv = 0; lv < kNumLevels; lv++) {
-    ver->v.lvl_begin[lv] = begin[lv];
-    ver->v.lvl_count[lv] = count[lv];
-    ver->v.lvl_sliced[lv] = lvl_sliced[lv];
+    ver->v.lvl_begin[lv] = P.begin[lv];
+    ver->v.lvl_count[lv] = P.count[lv];
+    ver->v.lvl_sliced[lv] = P.lvl_sliced[lv];
+  }
+  return DLSM_OK;
+}
+
+static int version_create_impl(dlsm_ctx* ctx, const dlsm_version_file* files, int n_files,
+                               int filters_are_device, const BlocksArg* ba, dlsm_version** out) {
+  if (!ctx || !out || n_files < 0 || (n_files > 0 && !files)) return DLSM_E_ARG;
+  *out = nullptr;
+  DLSM_CHECK(check_version_files(files, n_files));
+  DeviceGuard g(ctx->device);
+  // (sealed blocks: the device pass reads the tails)
+  std::vector<uint8_t> tails(5 * static_cast<size_t>(n_files));
+  for (int f = 0; f < n_files && !ba; f++)
+    if (files[f].filter && files[f].filter_len >= 5)
+      DLSM_CHECK(fetch_tail(ctx, files[f].filter, files[f].filter_len, filters_are_device, &tails[5 * f]));
+  const uint64_t min_bytes = ctx->vslice_bytes == 0 ? version_slice_min_bytes()
+                             : (ctx->vslice_bytes == UINT64_MAX ? 0 : ctx->vslice_bytes);
+  VersionPlan P;
+  DLSM_CHECK(plan_version(files, n_files, tails.data(), !ba, min_bytes, P));
+  dlsm_version* ver = new (std::nothrow) dlsm_version();
+  if (!ver) return DLSM_E_NOMEM;
+  ver->device = ctx->device;
+  ver->n_files = n_files;
+  std::vector<VFileDev> h;
+  const int st = version_upload(ctx, P, files, filters_are_device, ba, h, ver);
+  if (st != DLSM_OK) {
+    dlsm_version_destroy(ver);
+    return st;
   }
   *out = ver;
   return DLSM_OK;
@@ -2872,24 +2361,6 @@ int dlsm_version_probe_dev(dlsm_ctx* ctx, const dlsm_version* v, const dlsm_keys
 // ---------------------------------------------------------------------------
 // Legacy FilterPolicy format (util/bloom.cc)
 // ---------------------------------------------------------------------------
-namespace {
-// Tiles per legacy slice workgroup (log2): 16 (128 KiB of LDS, one workgroup
-// per CU) unless the batch then has fewer slices than the chip has CUs.
-int choose_legacy_tps_lg(const std::vector<uint32_t>& n_tiles) {
-  if (const char* e = getenv("DLSM_LEGACY_TPS_LG")) {
-    const int v = atoi(e);
-    if (v >= 0 && v <= 4) return v;
-  }
-  int lg = 4;
-  for (; lg > 0; lg--) {
-    uint64_t total = 0;
-    for (uint32_t t : n_tiles) total += (t + (1u << lg) - 1) >> lg;
-    if (total >= kBuildSliceCUs) break;
-  }
-  return lg;
-}
-}  // namespace
-
 int dlsm_bloom_legacy_build_dev(dlsm_ctx* ctx, const dlsm_build_job* jobs, int n_jobs,
                                 int bits_per_key, uint64_t* out_len_dev) {
   if (!ctx || n_jobs < 0 || (n_jobs > 0 && (!jobs || !out_len_dev))) return DLSM_E_ARG;
@@ -2900,7 +2371,7 @@ int dlsm_bloom_legacy_build_dev(dlsm_ctx* ctx, const dlsm_build_job* jobs, int n
   const int k = legacy_num_probes(bits_per_key);
   bool all_k20 = true, all_k28 = true;
   bool fits_a = k <= kLegacyKmaxA, fits_b = k <= kLegacyKmaxB;
-  uint64_t ws = 0, total = 0;
+  uint64_t ws = 0;
   std::vector<uint64_t> wpos(n_jobs), lens(n_jobs);
   std::vector<uint32_t> tiles(n_jobs), regions(n_jobs);
   for (int j = 0; j < n_jobs; j++) {
@@ -2925,36 +2396,14 @@ int dlsm_bloom_legacy_build_dev(dlsm_ctx* ctx, const dlsm_build_job* jobs, int n
   }
   const int mode = all_k20 ? KM_K20 : (all_k28 ? KM_K28 : KM_GENERIC);
   if (ctx->path != 1 && fits_b) {
-    const int tps_lg = choose_legacy_tps_lg(tiles);
-    std::vector<LegacyTileJobDev> hj(n_jobs);
-    std::vector<uint32_t> starts(2 * n_jobs);
-    uint64_t entry = 0, tabw = 0;
-    uint32_t chunk = 0, slice = 0;
-    for (int j = 0; j < n_jobs; j++) {
-      LegacyTileJobDev& d = hj[j];
-      const uint64_t bits = legacy_bits(jobs[j].keys.n, bits_per_key);
-      d.keys = to_desc(jobs[j].keys);
-      d.out = jobs[j].out;
-      d.out_len = out_len_dev + j;
-      d.entry0 = entry;
-      d.tab0 = tabw;
-      d.bits = static_cast<uint32_t>(bits);
-      d.magic = fastmod_magic(d.bits);
-      d.n_tiles = tiles[j];
-      d.region = regions[j];
-      d.n_chunks = ceil_div_u32(jobs[j].keys.n, kLegacyChunk);
-      d.chunk0 = chunk;
-      d.n_slices = (tiles[j] + (1u << tps_lg) - 1) >> tps_lg;
-      d.slice0 = slice;
-      d.k = k;
-      d.reserved = 0;
-      starts[j] = chunk;
-      starts[n_jobs + j] = slice;
-      entry += static_cast<uint64_t>(d.n_chunks) * d.region;
-      tabw += static_cast<uint64_t>(d.n_chunks) * (d.n_tiles + 1);
-      chunk += d.n_chunks;
-      slice += d.n_slices;
-    }
+    const char* tps = getenv("DLSM_LEGACY_TPS_LG");  // A/B knob
+    const int tps_lg = choose_legacy_tps_lg(tiles, tps ? atoi(tps) : -1);
+    const JobTable<LegacyTileJobDev> T =
+        plan_legacy_tile_jobs(jobs, n_jobs, bits_per_key, out_len_dev, tiles, regions, tps_lg, k);
+    const std::vector<LegacyTileJobDev>& hj = T.hj;
+    const std::vector<uint32_t>& starts = T.starts;
+    const uint64_t entry = T.entry, tabw = T.tabw;
+    const uint32_t chunk = T.chunk, slice = T.slice;
     DLSM_CHECK(ctx->ltjobs.ensure(n_jobs));
     DLSM_CHECK(ctx->ltstarts.ensure(2 * n_jobs));
     DLSM_CHECK(ctx->lentries.ensure(entry + 8));
@@ -2990,7 +2439,6 @@ int dlsm_bloom_legacy_build_dev(dlsm_ctx* ctx, const dlsm_build_job* jobs, int n
       key0s[q] = tk;
       tk += b.keys.n;
     }
-    total += tk;
     DLSM_CHECK(ctx->ljobs.ensure(nj));
     DLSM_CHECK(ctx->lstarts.ensure(nj));
     DLSM_CHECK(ctx_upload(ctx, ctx->ljobs.p, hj.data(), sizeof(LegacyJobDev) * nj, s));
@@ -3004,7 +2452,6 @@ int dlsm_bloom_legacy_build_dev(dlsm_ctx* ctx, const dlsm_build_job* jobs, int n
     DLSM_TRY(hipMemsetAsync(jobs[j].out + lens[j] - 1, static_cast<int>(static_cast<uint8_t>(k)), 1, s));
   }
   DLSM_CHECK(ctx_upload(ctx, out_len_dev, lens.data(), sizeof(uint64_t) * n_jobs, s));
-  (void)total;
   return DLSM_OK;
 }
 

@@ -1,4 +1,4 @@
-"""Packed filter images (bloom_capi.hip ProbeGroup::lgw, pack_filters_kernel,
+"""Packed filter images (host_plan.h ProbeGroup::lgw, pack_filters_kernel,
 probe_slice_kernel<LGR, LGW < 3>): a group of 1, 2 or 3-4 filters of one line
 count is probed from an image of W = 1, 2 or 4 bits per bit position (2,048 /
 1,024 / 512 lines per 128 KiB slice) instead of the byte-wide stacked image.

@@ -23,7 +23,7 @@ def test_slice_waves_4_to_15_large_groups(gpu, orc):
 
     import dlsm_amd
 
-    # the launch shape this exercises (bloom_capi.hip group_slices / slice_parts)
+    # the launch shape this exercises (host_plan.h group_slices / slice_parts)
     C, R = 8192, 256
     L = 31_251
     S = -(-L // R)
