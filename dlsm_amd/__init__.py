@@ -29,7 +29,7 @@ __all__ = [
     "BLOCK_TYPE", "BLOCK_FILTER", "device_available", "bloom_hash",
     "full_size", "legacy_size", "full_parse", "FullFilterBlockBuilder",
     "FullFilterBlockReader", "BloomFilterPolicy", "PATH_AUTO", "PATH_DIRECT", "PATH_SLICED",
-    "crc32c", "crc32c_mask", "Version", "VersionFile",
+    "crc32c", "crc32c_mask", "Version", "VersionFile", "PLAN_FIRST", "PLAN_ALL", "read_plan_chunk",
 ]
 
 PATH_AUTO, PATH_DIRECT, PATH_SLICED = 0, 1, 2
@@ -40,6 +40,7 @@ OPT_PROBE_CHUNK_LG, OPT_PROBE_SLICE_LG, OPT_BUILD_EXACT, OPT_PROBE_ROUND_SERIAL 
 OPT_FAULT_INJECT = 7  # test hook: builds / probes on the context return -value
 OPT_VERSION_SLICE_BYTES, OPT_VERSION_PASS_SLICES = 8, 9  # sliced version probe: level threshold, slices per pass
 OPT_PROBE_MULTI = 10  # multi-group filter sets: 1 one pass over every group (default), 0 a pass per group
+PLAN_FIRST, PLAN_ALL = 0, 1  # dlsm_version_read_plan_dev modes: each Get's lowest set slot / every set slot
 
 
 def lib():
@@ -53,6 +54,11 @@ def device_available() -> bool:
     except OSError:
         return False
     return n.value > 0
+
+
+def read_plan_chunk() -> int:
+    """Gets per workgroup-chunk of the read plan's kernels."""
+    return int(lib().dlsm_version_read_plan_chunk())
 
 
 def bloom_hash(key: bytes) -> int:
@@ -269,6 +275,7 @@ class Version:
             check(lib().dlsm_version_create(ctx.h, arr, n, 1 if on_device else 0, C.byref(h)),
                   "version_create")
         self.h = h
+        self.n_files = n
         a, b = C.c_int(), C.c_int()
         check(lib().dlsm_version_slots(h, C.byref(a), C.byref(b)), "version_slots")
         self.n_l0, self.n_slots = a.value, b.value
@@ -626,6 +633,37 @@ class Context:
         ks = keys.c()
         check(lib().dlsm_version_probe_dev(self.h, v.h, C.byref(ks), snapshot, _ptr(slot_mask),
                                            _ptr(level_file)), "version_probe_dev")
+
+    def version_read_plan_dev(self, v: Version, slot_mask, level_file, mode: int, file_begin, gets,
+                              dropped=None, *, n: Optional[int] = None, cap: Optional[int] = None):
+        """The probe's answers grouped by file (compressed sparse rows): gets
+        (device uint32[cap]) holds, for file f of the caller's ``files`` list, the
+        Gets that must read it at [file_begin[f], file_begin[f+1]), ascending;
+        file_begin (device uint64[n_files + 1]) is exact even when cap is too
+        small.  mode: PLAN_FIRST (each Get's lowest set slot) or PLAN_ALL;
+        dropped (device uint64[1], optional) counts malformed tasks.
+        Asynchronous; n defaults to slot_mask's length, cap to gets' length."""
+        n = int(slot_mask.numel()) if n is None else int(n)
+        cap = (0 if gets is None else int(gets.numel())) if cap is None else int(cap)
+        _need(slot_mask, 8 * n, "slot_mask")
+        if level_file is not None:
+            _need(level_file, 20 * n, "level_file")
+        _need(file_begin, 8 * (v.n_files + 1), "file_begin")
+        _need(gets, 4 * cap, "gets")
+        if dropped is not None:
+            _need(dropped, 8, "dropped")
+        check(lib().dlsm_version_read_plan_dev(self.h, v.h, _ptr(slot_mask), _ptr(level_file), n, mode,
+                                               _ptr(file_begin), _ptr(gets), cap, _ptr(dropped)),
+              "version_read_plan_dev")
+
+    def version_masks_advance_dev(self, slot_mask, hit, *, n: Optional[int] = None):
+        """Ends a read round: slot_mask[i] = 0 where hit[i] (device uint8[n]) is
+        non-zero, else slot_mask[i] without its lowest set bit.  Asynchronous."""
+        n = int(slot_mask.numel()) if n is None else int(n)
+        _need(slot_mask, 8 * n, "slot_mask")
+        _need(hit, n, "hit")
+        check(lib().dlsm_version_masks_advance_dev(self.h, _ptr(slot_mask), _ptr(hit), n),
+              "version_masks_advance_dev")
 
     # -- full filter probe --------------------------------------------------
     def filterset(self, filters, on_device: bool = False, *, sealed: bool = False,

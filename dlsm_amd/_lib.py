@@ -144,6 +144,9 @@ SIGNATURES = [
     ("dlsm_version_destroy", C.c_int, [_VP]),
     ("dlsm_version_slots", C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("dlsm_version_probe_dev", C.c_int, [_VP, _VP, C.POINTER(dlsm_keyset), C.c_uint64, _VP, _VP]),
+    ("dlsm_version_read_plan_dev", C.c_int, [_VP, _VP, _VP, _VP, C.c_uint64, C.c_int, _VP, _VP, C.c_uint64, _VP]),
+    ("dlsm_version_masks_advance_dev", C.c_int, [_VP, _VP, _VP, C.c_uint64]),
+    ("dlsm_version_read_plan_chunk", C.c_uint32, []),
     ("dlsm_bloom_full_probe", C.c_int, [_VP, _VP, C.POINTER(dlsm_keyset), _VP]),
     ("dlsm_bloom_full_probe_hashed_dev", C.c_int, [_VP, _VP, C.POINTER(dlsm_keyset), _VP]),
     ("dlsm_bloom_hash_batch", C.c_int, [C.POINTER(dlsm_keyset), _VP, C.c_int]),

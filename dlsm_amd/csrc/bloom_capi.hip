@@ -155,6 +155,7 @@ struct dlsm_ctx {
   uint64_t vplan_zeroed = 0;  // vplan's allocation generation whose counters were zeroed
   DevBuf<uint16_t> pos;
   DevBuf<uint8_t> smask;
+  DevBuf<uint8_t> plan_ws;  // read plan: tables and intermediate pairs (plan::ReadPlan's layout)
   // host-API staging
   DevBuf<uint8_t> st_keys;
   DevBuf<uint64_t> st_offs;
@@ -580,6 +581,7 @@ int dlsm_ctx_destroy(dlsm_ctx* ctx) {
   ctx->vabyte.release();
   ctx->vplan.release();
   ctx->smask.release();
+  ctx->plan_ws.release();
   ctx->sel.release();
   ctx->st_keys.release();
   ctx->st_offs.release();
@@ -802,7 +804,7 @@ int dlsm_ctx_stats(dlsm_ctx* ctx, uint64_t* device_allocs, uint64_t* device_byte
   add(ctx->entries); add(ctx->tab); add(ctx->jobs); add(ctx->starts); add(ctx->dchunk);
   add(ctx->jobL); add(ctx->ljobs); add(ctx->lstarts); add(ctx->ltjobs); add(ctx->ltstarts);
   add(ctx->lentries); add(ctx->ltab); add(ctx->pos); add(ctx->smask); add(ctx->hashes);
-  add(ctx->vgl); add(ctx->vabyte); add(ctx->vplan);
+  add(ctx->vgl); add(ctx->vabyte); add(ctx->vplan); add(ctx->plan_ws);
   add(ctx->st_keys); add(ctx->st_offs); add(ctx->st_out); add(ctx->st_len); add(ctx->st_filter);
   add(ctx->crc_streams); add(ctx->crc_partial); add(ctx->crc_tabs); add(ctx->crc_outp); add(ctx->crc_cap);
   add(ctx->crc_val); add(ctx->sel);
@@ -2129,8 +2131,9 @@ struct dlsm_version {
   int device = 0;
   VersionDev v{};
   int n_files = 0;
-  uint8_t* mem = nullptr;  // one allocation: files | key blob | filters (sliced levels: their images)
+  uint8_t* mem = nullptr;  // one allocation: files | key blob | filters (sliced levels: their images) | order
   std::vector<VersionLevel> sliced;
+  const uint32_t* order = nullptr;  // device: search order -> the caller's file index (the read plan's output names)
 };
 
 namespace {
@@ -2214,6 +2217,11 @@ static int version_upload(dlsm_ctx* ctx, const VersionPlan& P, const dlsm_versio
                             hipMemcpyHostToDevice, s));
   DLSM_TRY(hipMemcpyAsync(ver->mem + ivl_off, P.ivl.data(), sizeof(VIntervalDev) * P.ivl.size(),
                           hipMemcpyHostToDevice, s));
+  static_assert(sizeof(int) == sizeof(uint32_t), "VersionPlan::order uploads as u32");
+  if (n_files)
+    DLSM_TRY(hipMemcpyAsync(ver->mem + P.order_off, P.order.data(), sizeof(uint32_t) * n_files, hipMemcpyHostToDevice,
+                            s));
+  ver->order = reinterpret_cast<const uint32_t*>(ver->mem + P.order_off);
   DLSM_TRY(hipStreamSynchronize(s));  // pageable sources: finish before returning
   ver->v.files = reinterpret_cast<const VFileDev*>(ver->mem);
   ver->v.pre_small = reinterpret_cast<const ulonglong2*>(ver->mem + pre_off);
@@ -2355,6 +2363,78 @@ int dlsm_version_probe_dev(dlsm_ctx* ctx, const dlsm_version* v, const dlsm_keys
     DLSM_TRY(launch_version_unpermute(n, ctx->pos.p, ctx->smask.p, ctx->vabyte.p, slot_mask_dev, P.j, J, slots,
                                       p == 0, p + 1 == passes.size(), s));
   }
+  return DLSM_OK;
+}
+
+uint32_t dlsm_version_read_plan_chunk(void) { return kPlanChunk; }
+
+int dlsm_version_read_plan_dev(dlsm_ctx* ctx, const dlsm_version* v, const uint64_t* slot_mask_dev,
+                               const uint32_t* level_file_dev, uint64_t n, int mode, uint64_t* file_begin_dev,
+                               uint32_t* gets_dev, uint64_t cap, uint64_t* dropped_dev) {
+  if (!ctx || !v || v->device != ctx->device) return DLSM_E_ARG;
+  if (n > 0xffffffffull || (mode != DLSM_PLAN_FIRST && mode != DLSM_PLAN_ALL)) return DLSM_E_ARG;
+  if (!file_begin_dev || (!gets_dev && cap > 0)) return DLSM_E_ARG;
+  if (n > 0 && !slot_mask_dev) return DLSM_E_ARG;
+  const PlanShape shape = plan_shape(v->v.n_l0, v->v.lvl_begin, v->v.lvl_count);
+  bool level_files = false;
+  for (int lv = 0; lv < kPlanLevels; lv++) level_files = level_files || shape.lvl_count[lv] != 0;
+  if (n > 0 && !level_file_dev && level_files) return DLSM_E_ARG;
+  ReadPlan R;
+  DLSM_CHECK(plan_read(n, static_cast<uint64_t>(v->n_files), plan_tasks_per_get(shape), mode, R));
+  if (ctx->fault) return -ctx->fault;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = ctx->stream;
+  if (n == 0) {
+    DLSM_TRY(hipMemsetAsync(file_begin_dev, 0, sizeof(uint64_t) * (static_cast<uint64_t>(v->n_files) + 1), s));
+    if (dropped_dev) DLSM_TRY(hipMemsetAsync(dropped_dev, 0, sizeof(uint64_t), s));
+    return DLSM_OK;
+  }
+  DLSM_CHECK(ctx->plan_ws.ensure(R.bytes));
+  uint8_t* ws = ctx->plan_ws.p;
+  ReadPlanDev a{};
+  a.shape = shape;
+  a.order = v->order;
+  a.mask = slot_mask_dev;
+  a.pick = level_file_dev;
+  a.n = n;
+  a.n_files = static_cast<uint32_t>(v->n_files);
+  a.all = mode == DLSM_PLAN_ALL ? 1 : 0;
+  a.cnt = reinterpret_cast<uint32_t*>(ws + R.cnt_off);
+  a.off = reinterpret_cast<uint64_t*>(ws + R.off_off);
+  a.drop = reinterpret_cast<uint64_t*>(ws + R.drop_off);
+  a.total = reinterpret_cast<uint64_t*>(ws + R.total_off);
+  a.pair_items = R.pair_items;
+  a.file_begin = file_begin_dev;
+  a.gets = gets_dev;
+  a.cap = cap;
+  a.dropped = dropped_dev;
+  uint32_t* keys[2];
+  uint32_t* vals[2];
+  for (int b = 0; b < 2; b++) {
+    keys[b] = R.keys_bytes[b] ? reinterpret_cast<uint32_t*>(ws + R.keys_off[b]) : nullptr;
+    vals[b] = R.vals_bytes[b] ? reinterpret_cast<uint32_t*>(ws + R.vals_off[b]) : nullptr;
+  }
+  for (int p = 0; p < R.passes; p++) {
+    const ReadPlanPass& P = R.pass[p];
+    const bool last = p + 1 == R.passes;
+    // pass p writes buffer p % 2 and reads the other (pass 0: FIRST's file ids)
+    uint32_t* kin = keys[(p + 1) % 2];
+    const uint32_t* vin = p > 0 ? vals[(p + 1) % 2] : nullptr;
+    uint32_t* kout = R.passes > 1 ? keys[p % 2] : nullptr;  // (the last of several: the bounds kernel's input)
+    uint32_t* vout = last ? nullptr : vals[p % 2];
+    DLSM_TRY(launch_read_plan_pass(a, p, R.passes, P.shift, P.cpw, P.nwg, kin, vin, kout, vout, s));
+  }
+  if (R.passes > 1) DLSM_TRY(launch_read_plan_bounds(a, keys[(R.passes - 1) % 2], s));
+  return DLSM_OK;
+}
+
+int dlsm_version_masks_advance_dev(dlsm_ctx* ctx, uint64_t* slot_mask_dev, const uint8_t* hit_dev, uint64_t n) {
+  if (!ctx || n > 0xffffffffull) return DLSM_E_ARG;
+  if (n == 0) return DLSM_OK;
+  if (!slot_mask_dev || !hit_dev) return DLSM_E_ARG;
+  if (ctx->fault) return -ctx->fault;
+  DeviceGuard g(ctx->device);
+  DLSM_TRY(launch_masks_advance(slot_mask_dev, hit_dev, n, ctx->stream));
   return DLSM_OK;
 }
 

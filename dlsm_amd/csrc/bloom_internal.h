@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "bloom_math.h"
+#include "read_plan.h"
 
 namespace dlsm {
 
@@ -340,6 +341,38 @@ hipError_t launch_version_slices(const uint8_t* image, uint32_t L, int k, uint32
 hipError_t launch_version_unpermute(uint64_t n, const uint16_t* pos, const uint8_t* smask, uint8_t* abyte,
                                     uint64_t* slot_mask, int jbit, int n_sliced, uint64_t slots, bool first,
                                     bool last, hipStream_t s);
+// read_plan.hip: the read plan (dlsm_version_read_plan_dev), one digit pass of
+// its counting sort per call.  What the plan's kernels share across passes:
+struct ReadPlanDev {
+  PlanShape shape;
+  const uint32_t* order;       // search order -> the caller's file index (u32[n_files])
+  const uint64_t* mask;        // slot masks (n)
+  const uint32_t* pick;        // level picks (n x 5) or nullptr (no file on levels 1-5)
+  uint64_t n;
+  uint32_t n_files;
+  int32_t all;                 // DLSM_PLAN_ALL
+  uint32_t* cnt;               // u32[kPlanBins x table_wgs]
+  uint64_t* off;               // u64[kPlanBins x table_wgs]
+  uint64_t* drop;              // u64[table_wgs]
+  uint64_t* total;             // u64[1]
+  uint64_t pair_items;         // items each keys / vals buffer holds
+  uint64_t* file_begin;
+  uint32_t* gets;
+  uint64_t cap;
+  uint64_t* dropped;           // or nullptr
+};
+// Pass p of `passes` (shift, cpw, nwg from the planner): histogram, scan and
+// scatter launches.  keys_in / vals_in: the pairs the pass reads (pass 0:
+// FIRST's per-Get file ids, written by its histogram, or nullptr); keys_out /
+// vals_out: what it writes (the last pass: gets, and keys_out when the bounds
+// kernel needs the sorted ids; else nullptr).
+hipError_t launch_read_plan_pass(const ReadPlanDev& a, int p, int passes, uint32_t shift, uint32_t cpw,
+                                 uint32_t nwg, uint32_t* keys_in, const uint32_t* vals_in, uint32_t* keys_out,
+                                 uint32_t* vals_out, hipStream_t s);
+// file_begin of a plan of several passes: lower bounds in the sorted file ids.
+hipError_t launch_read_plan_bounds(const ReadPlanDev& a, const uint32_t* keys_sorted, hipStream_t s);
+hipError_t launch_masks_advance(uint64_t* mask, const uint8_t* hit, uint64_t n, hipStream_t s);
+
 hipError_t launch_filter_block_probe(const uint8_t* blk, uint64_t len, KeyDesc keys,
                                      const uint64_t* block_offsets, uint8_t* out, hipStream_t s);
 hipError_t launch_legacy_scatter(const LegacyJobDev* jobs, const uint64_t* key0s, int n_jobs,

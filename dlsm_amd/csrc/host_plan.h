@@ -10,6 +10,7 @@
 
 #include "../../include/dlsm_bloom.h"
 #include "bloom_internal.h"
+#include "read_plan.h"
 
 namespace dlsm {
 namespace plan {
@@ -507,7 +508,7 @@ struct VersionLevel {
 // Everything a version create computes before it allocates.  Per-file vectors
 // are in search order (order[j]: the caller's index of file j); offsets are
 // into the version's single allocation of `total` bytes:
-// VFileDev[n] | prefixes | key blob | bounds | intervals | filters / level images.
+// VFileDev[n] | prefixes | key blob | bounds | intervals | filters / level images | order.
 struct VersionPlan {
   std::vector<int> order;
   int n_l0 = 0;
@@ -520,6 +521,7 @@ struct VersionPlan {
   std::vector<uint64_t> foff, copy_len;  // per file: where its filter goes, and how much of it
   std::vector<VersionLevel> sliced;
   std::vector<uint64_t> image_off;  // per sliced level
+  uint64_t order_off = 0, order_bytes = 0;  // order[] as u32 (the read plan's file mapping), after the filters
   int32_t lvl_sliced[kNumLevels] = {};
   uint64_t total = 0;
   int k_all = 0;
@@ -718,9 +720,121 @@ inline int plan_version(const dlsm_version_file* files, int n_files, const uint8
     copy_len[j] = F.filter_len;
     total += (F.filter_len + 255) & ~uint64_t(255);
   }
+  P.order_off = total;
+  P.order_bytes = (sizeof(uint32_t) * static_cast<uint64_t>(n_files) + 255) & ~uint64_t(255);
+  total += P.order_bytes;
   P.total = total;
   P.k_all = version_k_all(files, order, h);
   return DLSM_OK;
+}
+
+// ---- read plan (read_plan.hip) ---------------------------------------------------
+// One digit pass of the plan's counting sort: its items (pass 0: the n Gets;
+// later passes: the tasks, of which the host knows only the bound items_max --
+// the kernels clip to the device-side total) are cut into chunks of kPlanChunk,
+// cpw chunks per workgroup, so that at most kPlanMaxWgs workgroups share the
+// (bin, workgroup) count table whatever n is.
+struct ReadPlanPass {
+  uint64_t items_max = 0;
+  uint64_t chunks = 0;
+  uint32_t cpw = 1;   // chunks per workgroup
+  uint32_t nwg = 0;   // workgroups (the grid); 0: nothing to do
+  uint32_t shift = 0; // the digit's first bit
+};
+
+// Everything dlsm_version_read_plan_dev computes before it launches: the
+// passes, and the workspace layout (byte offsets, every region 256-byte
+// aligned).  Buffer b of the key / Get-index pairs is written by pass p with
+// p % 2 == b; in DLSM_PLAN_FIRST mode the histogram of pass 0 leaves one file
+// id per Get in keys[1] for its scatter to read (4 B instead of mask + pick).
+struct ReadPlan {
+  int passes = 1;
+  uint32_t gets_per_chunk = kPlanChunk;  // C of the tests: Gets per workgroup-chunk of pass 0
+  uint64_t tasks_max = 0;                // bound on the tasks: n (FIRST) or n x tasks_per_get (ALL)
+  ReadPlanPass pass[kPlanMaxPasses];
+  uint32_t table_wgs = 1;    // workgroup rows of the tables: max nwg over the passes
+  uint64_t table_entries = 0;  // kPlanBins x table_wgs
+  uint64_t pair_items = 0;   // items of each keys / vals buffer in use
+  uint64_t cnt_off = 0, cnt_bytes = 0;    // u32[table_entries]: per (bin, workgroup) counts
+  uint64_t off_off = 0, off_bytes = 0;    // u64[table_entries]: their exclusive prefix sums
+  uint64_t drop_off = 0, drop_bytes = 0;  // u64[table_wgs]: per workgroup dropped tasks
+  uint64_t total_off = 0, total_bytes = 0;  // u64[1]: the task total
+  uint64_t keys_off[2] = {}, keys_bytes[2] = {};  // u32[pair_items] or unused (0 bytes)
+  uint64_t vals_off[2] = {}, vals_bytes[2] = {};
+  uint64_t bytes = 0;
+};
+
+// Digit passes that cover file ids 0 .. n_files-1.
+inline int read_plan_passes(uint64_t n_files) {
+  int bits = 0;
+  while (n_files > 1 && ((n_files - 1) >> bits) != 0) bits++;
+  return std::max(1, (bits + kPlanDigitLg - 1) / kPlanDigitLg);
+}
+
+inline ReadPlanPass read_plan_pass(uint64_t items_max, uint32_t shift) {
+  ReadPlanPass p;
+  p.items_max = items_max;
+  p.shift = shift;
+  p.chunks = (items_max + kPlanChunk - 1) / kPlanChunk;
+  p.cpw = static_cast<uint32_t>(std::max<uint64_t>(1, (p.chunks + kPlanMaxWgs - 1) / kPlanMaxWgs));
+  p.nwg = static_cast<uint32_t>((p.chunks + p.cpw - 1) / p.cpw);
+  return p;
+}
+
+// n Gets (<= UINT32_MAX) against a version of n_files files; tasks_per_get: the
+// most tasks one Get can have (FIRST: 1; ALL: level-0 files + non-empty levels).
+inline int plan_read(uint64_t n, uint64_t n_files, uint32_t tasks_per_get, int mode, ReadPlan& R) {
+  if (n > 0xffffffffull || n_files > 0x7fffffffull || (mode != DLSM_PLAN_FIRST && mode != DLSM_PLAN_ALL))
+    return DLSM_E_ARG;
+  if (tasks_per_get > 64) return DLSM_E_ARG;
+  R = ReadPlan();
+  R.passes = read_plan_passes(n_files);
+  R.tasks_max = mode == DLSM_PLAN_FIRST ? n : n * tasks_per_get;
+  R.pass[0] = read_plan_pass(n, 0);
+  for (int p = 1; p < R.passes; p++) R.pass[p] = read_plan_pass(R.tasks_max, static_cast<uint32_t>(p) * kPlanDigitLg);
+  for (int p = 0; p < R.passes; p++) R.table_wgs = std::max(R.table_wgs, R.pass[p].nwg);
+  R.table_entries = static_cast<uint64_t>(kPlanBins) * R.table_wgs;
+  auto pad = [](uint64_t b) { return (b + 255) & ~uint64_t(255); };
+  uint64_t at = 0;
+  auto region = [&](uint64_t* off, uint64_t* bytes, uint64_t want) {
+    *off = at;
+    *bytes = want;
+    at += pad(want);
+  };
+  region(&R.cnt_off, &R.cnt_bytes, sizeof(uint32_t) * R.table_entries);
+  region(&R.off_off, &R.off_bytes, sizeof(uint64_t) * R.table_entries);
+  region(&R.drop_off, &R.drop_bytes, sizeof(uint64_t) * R.table_wgs);
+  region(&R.total_off, &R.total_bytes, sizeof(uint64_t));
+  // keys[1]: FIRST's per-Get file ids, and pass 1's output; the rest only for
+  // several passes (vals[1]: written by pass 1 when a pass 2 reads it)
+  const bool multi = R.passes > 1;
+  R.pair_items = R.tasks_max;
+  const uint64_t pb = sizeof(uint32_t) * R.pair_items;
+  region(&R.keys_off[0], &R.keys_bytes[0], multi ? pb : 0);
+  region(&R.vals_off[0], &R.vals_bytes[0], multi ? pb : 0);
+  region(&R.keys_off[1], &R.keys_bytes[1], (multi || mode == DLSM_PLAN_FIRST) ? pb : 0);
+  region(&R.vals_off[1], &R.vals_bytes[1], R.passes > 2 ? pb : 0);
+  R.bytes = at;
+  return DLSM_OK;
+}
+
+// The decoder's view of a version (levels 1..5 of begin / count).
+inline PlanShape plan_shape(uint32_t n_l0, const uint32_t* begin, const uint32_t* count) {
+  PlanShape s{};
+  s.n_l0 = n_l0;
+  s.n_slots = n_l0 + kPlanLevels;
+  for (int lv = 1; lv < kNumLevels; lv++) {
+    s.lvl_begin[lv - 1] = begin[lv];
+    s.lvl_count[lv - 1] = count[lv];
+  }
+  return s;
+}
+
+// The most tasks one Get can have in DLSM_PLAN_ALL mode.
+inline uint32_t plan_tasks_per_get(const PlanShape& s) {
+  uint32_t t = s.n_l0;
+  for (int lv = 0; lv < kPlanLevels; lv++) t += s.lvl_count[lv] ? 1u : 0u;
+  return t;
 }
 
 }  // namespace plan

@@ -188,8 +188,8 @@ int dlsm_ctx_set_path(dlsm_ctx* ctx, int path);
  *   DLSM_OPT_PROBE_ROUND_SERIAL 1: probe rounds run one after another on the context
  *                             stream (one buffer set) instead of pipelined over two
  *                             streams (default 0, or $DLSM_PROBE_SERIAL)
- *   DLSM_OPT_FAULT_INJECT     test hook: v > 0 makes every build and probe call on the
- *                             context return -v (4 = DLSM_E_DEVICE, 5 = DLSM_E_NOMEM)
+ *   DLSM_OPT_FAULT_INJECT     test hook: v > 0 makes every build, probe and read-plan call on
+ *                             the context return -v (4 = DLSM_E_DEVICE, 5 = DLSM_E_NOMEM)
  *                             before touching the device; 0 (default) off
  *   DLSM_OPT_VERSION_SLICE_BYTES  EXPERIMENTAL (off by default, kept with its tests):
  *                             dlsm_version_create on this context: a level >= 1 whose
@@ -512,6 +512,44 @@ int dlsm_version_slots(const dlsm_version* v, int* n_l0, int* n_slots);
  * candidate file, UINT32_MAX when the level has none.  Asynchronous. */
 int dlsm_version_probe_dev(dlsm_ctx* ctx, const dlsm_version* v, const dlsm_keyset* keys,
                            uint64_t snapshot, uint64_t* slot_mask_dev, uint32_t* level_file_dev);
+
+/* The read plan of a probed batch: the probe's answers grouped by file, so the
+ * caller reads each SSTable's data blocks for all its Gets at once.  A set bit
+ * s of slot_mask_dev[i] is one task (Get i, file): level-0 file s in search
+ * order for s < n_l0, else file number level_file_dev[i*5 + level-1] inside
+ * level = s - n_l0 + 1.  Files are named by the caller's index in the files[]
+ * array given to dlsm_version_create[_blocks].  Compressed sparse rows:
+ * gets_dev[file_begin_dev[f] .. file_begin_dev[f+1]) are the Get indices of
+ * file f's tasks in strictly ascending order, file_begin_dev[n_files] is the
+ * task total -- a pure function of the inputs.
+ *   mode  DLSM_PLAN_FIRST  per Get only its lowest set slot: the file it reads
+ *                          next (cap = n always suffices)
+ *         DLSM_PLAN_ALL    every set slot
+ *   file_begin_dev  device u64[n_files + 1], always exact
+ *   gets_dev        device u32[cap]; entries at positions >= cap are not
+ *                   written, everything below cap is correct: the caller
+ *                   compares file_begin_dev[n_files] with cap after its sync
+ *   dropped_dev     device u64[1] or NULL: the tasks dropped as malformed -- a
+ *                   slot >= n_slots, or a level pick >= that level's file count
+ *                   (UINT32_MAX included); such a task is never clamped to a file
+ * level_file_dev may be NULL only when the version has no file on levels 1-5.
+ * n <= UINT32_MAX; n == 0 writes an all-zero file_begin_dev.  Works for every
+ * version the probe accepts.  Asynchronous on the context's stream: no host
+ * read-back, no synchronisation. */
+#define DLSM_PLAN_FIRST 0
+#define DLSM_PLAN_ALL 1
+int dlsm_version_read_plan_dev(dlsm_ctx* ctx, const dlsm_version* v, const uint64_t* slot_mask_dev,
+                               const uint32_t* level_file_dev, uint64_t n, int mode, uint64_t* file_begin_dev,
+                               uint32_t* gets_dev, uint64_t cap, uint64_t* dropped_dev);
+/* Ends a read round: mask[i] = hit[i] ? 0 : mask[i] & (mask[i] - 1) (hit_dev:
+ * device u8[n], non-zero where the Get found its key in the file just read).
+ * The loop probe -> plan(FIRST) -> read -> advance -> plan(FIRST) ... visits
+ * each Get's files in Version::Get's order and ends when a plan's total is 0.
+ * Asynchronous. */
+int dlsm_version_masks_advance_dev(dlsm_ctx* ctx, uint64_t* slot_mask_dev, const uint8_t* hit_dev, uint64_t n);
+/* Gets per workgroup-chunk of the plan's kernels (the sizes around which its
+ * tests are built). */
+uint32_t dlsm_version_read_plan_chunk(void);
 
 /* ---- legacy FilterPolicy format (util/bloom.cc) ------------------------- */
 
