@@ -30,6 +30,7 @@ __all__ = [
     "full_size", "legacy_size", "full_parse", "FullFilterBlockBuilder",
     "FullFilterBlockReader", "BloomFilterPolicy", "PATH_AUTO", "PATH_DIRECT", "PATH_SLICED",
     "crc32c", "crc32c_mask", "Version", "VersionFile", "PLAN_FIRST", "PLAN_ALL", "read_plan_chunk",
+    "ShardMap", "MAX_SHARDS", "ROUTE_ALIGN", "shard_route_cap", "shard_route_chunk",
 ]
 
 PATH_AUTO, PATH_DIRECT, PATH_SLICED = 0, 1, 2
@@ -41,6 +42,7 @@ OPT_FAULT_INJECT = 7  # test hook: builds / probes on the context return -value
 OPT_VERSION_SLICE_BYTES, OPT_VERSION_PASS_SLICES = 8, 9  # sliced version probe: level threshold, slices per pass
 OPT_PROBE_MULTI = 10  # multi-group filter sets: 1 one pass over every group (default), 0 a pass per group
 PLAN_FIRST, PLAN_ALL = 0, 1  # dlsm_version_read_plan_dev modes: each Get's lowest set slot / every set slot
+MAX_SHARDS, ROUTE_ALIGN = 511, 4  # DLSM_MAX_SHARDS, DLSM_ROUTE_ALIGN
 
 
 def lib():
@@ -59,6 +61,17 @@ def device_available() -> bool:
 def read_plan_chunk() -> int:
     """Gets per workgroup-chunk of the read plan's kernels."""
     return int(lib().dlsm_version_read_plan_chunk())
+
+
+def shard_route_chunk() -> int:
+    """Gets per workgroup-chunk of the shard route's kernels."""
+    return int(lib().dlsm_shard_route_chunk())
+
+
+def shard_route_cap(n: int, n_shards: int) -> int:
+    """Slots of ``gets`` (and rows of ``keys_out``) a route of n Gets over
+    n_shards shards needs: n + 3 per bin, rounded up to ROUTE_ALIGN."""
+    return int(lib().dlsm_shard_route_cap(n, n_shards))
 
 
 def bloom_hash(key: bytes) -> int:
@@ -283,6 +296,30 @@ class Version:
     def close(self):
         if getattr(self, "h", None):
             lib().dlsm_version_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+class ShardMap:
+    """The upper bounds of a sharded database's shards resident on one device
+    (DBImpl_Sharding's shards_pool keys, db/db_impl_sharding.cpp:9-35):
+    ``bounds`` strictly ascending byte strings, 1..MAX_SHARDS of them."""
+
+    def __init__(self, ctx: "Context", bounds: Sequence[bytes]):
+        n = len(bounds)
+        arrs = [np.frombuffer(bytes(b) + b"\0", dtype=np.uint8) for b in bounds]
+        pa = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
+        la = (C.c_uint64 * max(n, 1))(*[len(b) for b in bounds])
+        h = C.c_void_p()
+        check(lib().dlsm_shardmap_create(ctx.h, pa, la, n, C.byref(h)), "shardmap_create")
+        self.h = h
+        self.n_shards = n
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().dlsm_shardmap_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -664,6 +701,29 @@ class Context:
         _need(hit, n, "hit")
         check(lib().dlsm_version_masks_advance_dev(self.h, _ptr(slot_mask), _ptr(hit), n),
               "version_masks_advance_dev")
+
+    # -- shard route: the first step of a sharded Get ---------------------------
+    def shardmap(self, bounds: Sequence[bytes]) -> ShardMap:
+        return ShardMap(self, bounds)
+
+    def shard_route_dev(self, m: ShardMap, keys: Keys, shard_off, shard_cnt, gets, keys_out=None, *,
+                        cap: Optional[int] = None):
+        """Get_Target_Shard for a device Get batch: bin s (shard s, or
+        n_shards = "no shard") owns gets[shard_off[s] : shard_off[s] +
+        shard_cnt[s]] (device uint32[cap]), the bin's Get indices ascending;
+        shard_off / shard_cnt are device uint64[n_shards + 1], every offset a
+        multiple of ROUTE_ALIGN.  keys_out (device uint8[cap * key_len],
+        fixed-length keys only): key gets[p] copied to row p.  Asynchronous;
+        cap defaults to gets' length and must be >= shard_route_cap(n, n_shards)."""
+        cap = (0 if gets is None else int(gets.numel())) if cap is None else int(cap)
+        _need(shard_off, 8 * (m.n_shards + 1), "shard_off")
+        _need(shard_cnt, 8 * (m.n_shards + 1), "shard_cnt")
+        _need(gets, 4 * cap, "gets")
+        if keys_out is not None:
+            _need(keys_out, cap * keys.key_len, "keys_out")
+        ks = keys.c()
+        check(lib().dlsm_shard_route_dev(self.h, m.h, C.byref(ks), _ptr(shard_off), _ptr(shard_cnt), _ptr(gets),
+                                         _ptr(keys_out), cap), "shard_route_dev")
 
     # -- full filter probe --------------------------------------------------
     def filterset(self, filters, on_device: bool = False, *, sealed: bool = False,

@@ -147,6 +147,13 @@ SIGNATURES = [
     ("dlsm_version_read_plan_dev", C.c_int, [_VP, _VP, _VP, _VP, C.c_uint64, C.c_int, _VP, _VP, C.c_uint64, _VP]),
     ("dlsm_version_masks_advance_dev", C.c_int, [_VP, _VP, _VP, C.c_uint64]),
     ("dlsm_version_read_plan_chunk", C.c_uint32, []),
+    ("dlsm_shardmap_create", C.c_int, [_VP, C.POINTER(_VP), _U64P, C.c_int, C.POINTER(_VP)]),
+    ("dlsm_shardmap_destroy", C.c_int, [_VP]),
+    ("dlsm_shardmap_size", C.c_int, [_VP, C.POINTER(C.c_int)]),
+    ("dlsm_shard_route_dev", C.c_int, [_VP, _VP, C.POINTER(dlsm_keyset), _VP, _VP, _VP, _VP, C.c_uint64]),
+    ("dlsm_shard_route", C.c_int, [_VP, _VP, C.POINTER(dlsm_keyset), _VP, _VP, _VP, _VP, C.c_uint64]),
+    ("dlsm_shard_route_cap", C.c_uint64, [C.c_uint64, C.c_int]),
+    ("dlsm_shard_route_chunk", C.c_uint32, []),
     ("dlsm_bloom_full_probe", C.c_int, [_VP, _VP, C.POINTER(dlsm_keyset), _VP]),
     ("dlsm_bloom_full_probe_hashed_dev", C.c_int, [_VP, _VP, C.POINTER(dlsm_keyset), _VP]),
     ("dlsm_bloom_hash_batch", C.c_int, [C.POINTER(dlsm_keyset), _VP, C.c_int]),

@@ -156,6 +156,7 @@ struct dlsm_ctx {
   DevBuf<uint16_t> pos;
   DevBuf<uint8_t> smask;
   DevBuf<uint8_t> plan_ws;  // read plan: tables and intermediate pairs (plan::ReadPlan's layout)
+  DevBuf<uint8_t> route_ws;  // shard route: the Gets' bins and the tables (plan::ShardRoute's layout)
   // host-API staging
   DevBuf<uint8_t> st_keys;
   DevBuf<uint64_t> st_offs;
@@ -582,6 +583,7 @@ int dlsm_ctx_destroy(dlsm_ctx* ctx) {
   ctx->vplan.release();
   ctx->smask.release();
   ctx->plan_ws.release();
+  ctx->route_ws.release();
   ctx->sel.release();
   ctx->st_keys.release();
   ctx->st_offs.release();
@@ -804,7 +806,7 @@ int dlsm_ctx_stats(dlsm_ctx* ctx, uint64_t* device_allocs, uint64_t* device_byte
   add(ctx->entries); add(ctx->tab); add(ctx->jobs); add(ctx->starts); add(ctx->dchunk);
   add(ctx->jobL); add(ctx->ljobs); add(ctx->lstarts); add(ctx->ltjobs); add(ctx->ltstarts);
   add(ctx->lentries); add(ctx->ltab); add(ctx->pos); add(ctx->smask); add(ctx->hashes);
-  add(ctx->vgl); add(ctx->vabyte); add(ctx->vplan); add(ctx->plan_ws);
+  add(ctx->vgl); add(ctx->vabyte); add(ctx->vplan); add(ctx->plan_ws); add(ctx->route_ws);
   add(ctx->st_keys); add(ctx->st_offs); add(ctx->st_out); add(ctx->st_len); add(ctx->st_filter);
   add(ctx->crc_streams); add(ctx->crc_partial); add(ctx->crc_tabs); add(ctx->crc_outp); add(ctx->crc_cap);
   add(ctx->crc_val); add(ctx->sel);
@@ -2435,6 +2437,150 @@ int dlsm_version_masks_advance_dev(dlsm_ctx* ctx, uint64_t* slot_mask_dev, const
   if (ctx->fault) return -ctx->fault;
   DeviceGuard g(ctx->device);
   DLSM_TRY(launch_masks_advance(slot_mask_dev, hit_dev, n, ctx->stream));
+  return DLSM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Shard route: DBImpl_Sharding::Get_Target_Shard for a Get batch
+// ---------------------------------------------------------------------------
+static_assert(DLSM_MAX_SHARDS == kRouteBins - 1 && DLSM_ROUTE_ALIGN == kRouteAlign, "shard route constants");
+
+struct dlsm_shardmap {
+  int device = 0;
+  int n_shards = 0;
+  uint8_t* mem = nullptr;  // one allocation: prefixes | byte offsets | bytes (plan::ShardMapImage)
+  RouteBounds b{};         // device pointers into mem
+};
+
+int dlsm_shardmap_create(dlsm_ctx* ctx, const uint8_t* const* upper_bounds, const uint64_t* lens, int n_shards,
+                         dlsm_shardmap** out) {
+  if (!out) return DLSM_E_ARG;
+  *out = nullptr;
+  ShardMapImage M;
+  DLSM_CHECK(plan_shardmap(upper_bounds, lens, n_shards, M));
+  if (!ctx) return DLSM_E_ARG;
+  DeviceGuard g(ctx->device);
+  uint8_t* mem = nullptr;
+  DLSM_TRY(hipMalloc(reinterpret_cast<void**>(&mem), M.total));
+  hipStream_t s = ctx->stream;
+  hipError_t e = hipMemcpyAsync(mem + M.pre_off, M.pre.data(), sizeof(RoutePrefix) * M.pre.size(),
+                                hipMemcpyHostToDevice, s);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(mem + M.off_off, M.off.data(), sizeof(uint64_t) * M.off.size(), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && !M.bytes.empty())
+    e = hipMemcpyAsync(mem + M.bytes_off, M.bytes.data(), M.bytes.size(), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = ctx_sync(ctx, s);  // the image is pageable host memory
+  if (e != hipSuccess) {
+    (void)hipFree(mem);
+    return from_hip(e);
+  }
+  dlsm_shardmap* m = new (std::nothrow) dlsm_shardmap;
+  if (!m) {
+    (void)hipFree(mem);
+    return DLSM_E_NOMEM;
+  }
+  m->device = ctx->device;
+  m->n_shards = n_shards;
+  m->mem = mem;
+  m->b.pre = reinterpret_cast<const RoutePrefix*>(mem + M.pre_off);
+  m->b.off = reinterpret_cast<const uint64_t*>(mem + M.off_off);
+  m->b.bytes = mem + M.bytes_off;
+  m->b.n = static_cast<uint32_t>(n_shards);
+  *out = m;
+  return DLSM_OK;
+}
+
+int dlsm_shardmap_destroy(dlsm_shardmap* m) {
+  if (!m) return DLSM_OK;
+  DeviceGuard g(m->device);
+  if (m->mem) (void)hipFree(m->mem);
+  delete m;
+  return DLSM_OK;
+}
+
+int dlsm_shardmap_size(const dlsm_shardmap* m, int* n_shards) {
+  if (!m) return DLSM_E_ARG;
+  if (n_shards) *n_shards = m->n_shards;
+  return DLSM_OK;
+}
+
+uint64_t dlsm_shard_route_cap(uint64_t n, int n_shards) { return shard_route_cap(n, n_shards < 0 ? 0 : n_shards); }
+
+uint32_t dlsm_shard_route_chunk(void) { return kRouteChunk; }
+
+int dlsm_shard_route_dev(dlsm_ctx* ctx, const dlsm_shardmap* map, const dlsm_keyset* keys, uint64_t* shard_off_dev,
+                         uint64_t* shard_cnt_dev, uint32_t* gets_dev, uint8_t* keys_out_dev, uint64_t cap) {
+  if (!ctx || !map || !keys || map->device != ctx->device) return DLSM_E_ARG;
+  if (!shard_off_dev || !shard_cnt_dev) return DLSM_E_ARG;
+  DLSM_CHECK(validate_keyset(*keys));
+  const uint64_t n = keys->n;
+  if (keys_out_dev && keys->offsets) return DLSM_E_ARG;  // variable-length keys: the indices only
+  ShardRoute R;
+  DLSM_CHECK(plan_shard_route(n, map->n_shards, kRouteMaxWgs, R));
+  if (cap < shard_route_cap(n, map->n_shards) || (n > 0 && !gets_dev)) return DLSM_E_ARG;
+  if (ctx->fault) return -ctx->fault;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = ctx->stream;
+  if (n == 0) {
+    DLSM_TRY(hipMemsetAsync(shard_off_dev, 0, sizeof(uint64_t) * R.bins, s));
+    DLSM_TRY(hipMemsetAsync(shard_cnt_dev, 0, sizeof(uint64_t) * R.bins, s));
+    return DLSM_OK;
+  }
+  DLSM_CHECK(ctx->route_ws.ensure(R.bytes));
+  uint8_t* ws = ctx->route_ws.p;
+  ShardRouteDev a{};
+  a.bounds = map->b;
+  a.keys = to_desc(*keys);
+  a.bins = R.bins;
+  a.cpw = R.cpw;
+  a.nwg = R.nwg;
+  a.ids = reinterpret_cast<uint16_t*>(ws + R.ids_off);
+  a.cnt = reinterpret_cast<uint32_t*>(ws + R.cnt_off);
+  a.off = reinterpret_cast<uint64_t*>(ws + R.off_off);
+  a.shard_off = shard_off_dev;
+  a.shard_cnt = shard_cnt_dev;
+  a.gets = gets_dev;
+  a.keys_out = keys_out_dev;
+  a.cap = cap;
+  DLSM_TRY(launch_shard_route(a, s));
+  return DLSM_OK;
+}
+
+int dlsm_shard_route(dlsm_ctx* ctx, const dlsm_shardmap* map, const dlsm_keyset* keys, uint64_t* shard_off,
+                     uint64_t* shard_cnt, uint32_t* gets, uint8_t* keys_out, uint64_t cap) {
+  if (!ctx || !map || !keys || !shard_off || !shard_cnt) return DLSM_E_ARG;
+  DLSM_CHECK(validate_keyset(*keys));
+  if (keys_out && keys->offsets) return DLSM_E_ARG;
+  const uint64_t n = keys->n, bins = static_cast<uint64_t>(map->n_shards) + 1;
+  if (n > 0xffffffffull || cap < shard_route_cap(n, map->n_shards) || (n > 0 && !gets)) return DLSM_E_ARG;
+  if (ctx->fault) return -ctx->fault;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = ctx->stream;
+  const dlsm_keyset* sets[1] = {keys};
+  std::vector<dlsm_keyset> dk;
+  DLSM_CHECK(stage_keys(ctx, sets, 1, dk));
+  // staging: [shard_off | shard_cnt | gets | keys_out], each 256-byte aligned
+  auto pad = [](uint64_t b) { return (b + 255) & ~uint64_t(255); };
+  const uint64_t co = pad(8 * bins), go = co + pad(8 * bins), ko = go + pad(4 * cap);
+  const uint64_t kb = keys_out ? cap * keys->key_len : 0;
+  DLSM_CHECK(ctx->st_out.ensure(ko + kb));
+  uint8_t* st = ctx->st_out.p;
+  DLSM_CHECK(dlsm_shard_route_dev(ctx, map, &dk[0], reinterpret_cast<uint64_t*>(st),
+                                  reinterpret_cast<uint64_t*>(st + co), reinterpret_cast<uint32_t*>(st + go),
+                                  keys_out ? st + ko : nullptr, cap));
+  DLSM_TRY(hipMemcpyAsync(shard_off, st, 8 * bins, hipMemcpyDeviceToHost, s));
+  DLSM_TRY(hipMemcpyAsync(shard_cnt, st + co, 8 * bins, hipMemcpyDeviceToHost, s));
+  DLSM_TRY(ctx_sync(ctx, s));
+  // only the runs are defined: the gaps are copied as they are and the caller's
+  // gap slots keep what the device staging held, so copy run by run
+  for (uint64_t b = 0; b < bins; b++) {
+    if (!shard_cnt[b]) continue;
+    DLSM_TRY(hipMemcpyAsync(gets + shard_off[b], st + go + 4 * shard_off[b], 4 * shard_cnt[b], hipMemcpyDeviceToHost, s));
+    if (keys_out)
+      DLSM_TRY(hipMemcpyAsync(keys_out + shard_off[b] * keys->key_len, st + ko + shard_off[b] * keys->key_len,
+                              shard_cnt[b] * keys->key_len, hipMemcpyDeviceToHost, s));
+  }
+  DLSM_TRY(ctx_sync(ctx, s));
   return DLSM_OK;
 }
 

@@ -7,6 +7,7 @@
 
 #include "bloom_math.h"
 #include "read_plan.h"
+#include "shard_route.h"
 
 namespace dlsm {
 
@@ -372,6 +373,24 @@ hipError_t launch_read_plan_pass(const ReadPlanDev& a, int p, int passes, uint32
 // file_begin of a plan of several passes: lower bounds in the sorted file ids.
 hipError_t launch_read_plan_bounds(const ReadPlanDev& a, const uint32_t* keys_sorted, hipStream_t s);
 hipError_t launch_masks_advance(uint64_t* mask, const uint8_t* hit, uint64_t n, hipStream_t s);
+
+// shard_route.hip: the shard route (dlsm_shard_route_dev).  The count, scan and
+// scatter launches of its one counting-sort pass (cpw, nwg from the planner).
+struct ShardRouteDev {
+  RouteBounds bounds;          // device pointers (dlsm_shardmap)
+  KeyDesc keys;
+  uint32_t bins;               // bounds.n + 1
+  uint32_t cpw, nwg;
+  uint16_t* ids;               // u16[n]: every Get's bin
+  uint32_t* cnt;               // u32[bins x nwg]
+  uint64_t* off;               // u64[bins x nwg]
+  uint64_t* shard_off;         // u64[bins]
+  uint64_t* shard_cnt;         // u64[bins]
+  uint32_t* gets;              // u32[cap]
+  uint8_t* keys_out;           // cap x key_len bytes or nullptr
+  uint64_t cap;
+};
+hipError_t launch_shard_route(const ShardRouteDev& a, hipStream_t s);
 
 hipError_t launch_filter_block_probe(const uint8_t* blk, uint64_t len, KeyDesc keys,
                                      const uint64_t* block_offsets, uint8_t* out, hipStream_t s);

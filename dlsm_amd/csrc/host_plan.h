@@ -837,5 +837,92 @@ inline uint32_t plan_tasks_per_get(const PlanShape& s) {
   return t;
 }
 
+// ---- shard route (shard_route.hip) -----------------------------------------------
+// The route's one counting-sort pass: the n Gets cut into chunks of kRouteChunk,
+// cpw chunks per workgroup, so that at most max_wgs (the ABI: kRouteMaxWgs)
+// workgroups share the (bin, workgroup) count table whatever n is; and the
+// workspace layout (byte offsets, every region 256-byte aligned).
+struct ShardRoute {
+  uint32_t bins = 0;     // n_shards + 1: the shards and the "no shard" bin
+  uint64_t chunks = 0;
+  uint32_t cpw = 1;      // chunks per workgroup
+  uint32_t nwg = 0;      // workgroups (the grid); 0: nothing to do
+  uint64_t table_entries = 0;               // bins x nwg
+  uint64_t ids_off = 0, ids_bytes = 0;      // u16[n]: every Get's bin (the count pass writes them)
+  uint64_t cnt_off = 0, cnt_bytes = 0;      // u32[table_entries]: per (bin, workgroup) counts
+  uint64_t off_off = 0, off_bytes = 0;      // u64[table_entries]: the first output position of each
+  uint64_t bytes = 0;
+};
+
+// dlsm_shard_route_cap: every bin's run starts at a multiple of kRouteAlign, so
+// each of the n_shards + 1 bins wastes at most kRouteAlign - 1 slots.
+inline uint64_t shard_route_cap(uint64_t n, int n_shards) {
+  const uint64_t c = n + static_cast<uint64_t>(kRouteAlign - 1) * (static_cast<uint64_t>(n_shards) + 1);
+  return (c + kRouteAlign - 1) & ~static_cast<uint64_t>(kRouteAlign - 1);
+}
+
+// The padded-offset arithmetic of the scan kernel: off[s] = the previous bin's
+// end rounded up to kRouteAlign.  Returns the last bin's end rounded up.
+inline uint64_t shard_route_offsets(const uint64_t* cnt, uint32_t bins, uint64_t* off) {
+  uint64_t at = 0;
+  for (uint32_t s = 0; s < bins; s++) {
+    off[s] = at;
+    at = (at + cnt[s] + kRouteAlign - 1) & ~static_cast<uint64_t>(kRouteAlign - 1);
+  }
+  return at;
+}
+
+inline int plan_shard_route(uint64_t n, int n_shards, uint32_t max_wgs, ShardRoute& R) {
+  if (n > 0xffffffffull || n_shards < 1 || n_shards > static_cast<int>(kRouteBins) - 1 || max_wgs == 0)
+    return DLSM_E_ARG;
+  R = ShardRoute();
+  R.bins = static_cast<uint32_t>(n_shards) + 1;
+  R.chunks = (n + kRouteChunk - 1) / kRouteChunk;
+  R.cpw = static_cast<uint32_t>(std::max<uint64_t>(1, (R.chunks + max_wgs - 1) / max_wgs));
+  R.nwg = static_cast<uint32_t>((R.chunks + R.cpw - 1) / R.cpw);
+  R.table_entries = static_cast<uint64_t>(R.bins) * R.nwg;
+  auto pad = [](uint64_t b) { return (b + 255) & ~uint64_t(255); };
+  uint64_t at = 0;
+  auto region = [&](uint64_t* off, uint64_t* bytes, uint64_t want) {
+    *off = at;
+    *bytes = want;
+    at += pad(want);
+  };
+  region(&R.ids_off, &R.ids_bytes, sizeof(uint16_t) * n);
+  region(&R.cnt_off, &R.cnt_bytes, sizeof(uint32_t) * R.table_entries);
+  region(&R.off_off, &R.off_bytes, sizeof(uint64_t) * R.table_entries);
+  R.bytes = at;
+  return DLSM_OK;
+}
+
+// dlsm_shardmap_create's checks and the map's device image: the bounds'
+// prefixes, their byte offsets and their bytes.  DLSM_E_ARG unless the bounds
+// are strictly ascending under Slice::compare.
+struct ShardMapImage {
+  std::vector<RoutePrefix> pre;
+  std::vector<uint64_t> off;   // n + 1
+  std::vector<uint8_t> bytes;
+  uint64_t pre_off = 0, off_off = 0, bytes_off = 0, total = 0;  // 256-byte aligned regions
+};
+
+inline int plan_shardmap(const uint8_t* const* bounds, const uint64_t* lens, int n_shards, ShardMapImage& M) {
+  if (!bounds || !lens || n_shards < 1 || n_shards > static_cast<int>(kRouteBins) - 1) return DLSM_E_ARG;
+  M = ShardMapImage();
+  M.off.assign(1, 0);
+  for (int i = 0; i < n_shards; i++) {
+    if (lens[i] && !bounds[i]) return DLSM_E_ARG;
+    if (i > 0 && route_compare(bounds[i - 1], lens[i - 1], bounds[i], lens[i]) >= 0) return DLSM_E_ARG;
+    M.pre.push_back(route_prefix(bounds[i], lens[i]));
+    if (lens[i]) M.bytes.insert(M.bytes.end(), bounds[i], bounds[i] + lens[i]);
+    M.off.push_back(M.bytes.size());
+  }
+  auto pad = [](uint64_t b) { return (b + 255) & ~uint64_t(255); };
+  M.pre_off = 0;
+  M.off_off = pad(sizeof(RoutePrefix) * M.pre.size());
+  M.bytes_off = M.off_off + pad(sizeof(uint64_t) * M.off.size());
+  M.total = M.bytes_off + pad(std::max<size_t>(1, M.bytes.size()));
+  return DLSM_OK;
+}
+
 }  // namespace plan
 }  // namespace dlsm

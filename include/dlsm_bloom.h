@@ -551,6 +551,78 @@ int dlsm_version_masks_advance_dev(dlsm_ctx* ctx, uint64_t* slot_mask_dev, const
  * tests are built). */
 uint32_t dlsm_version_read_plan_chunk(void);
 
+/* ---- shard route: the first step of a sharded Get ----------------------- */
+
+/* With more than one memory node, or --fixed_compute_shards_num set, the
+ * reference database is not one DBImpl: benchmarks/db_bench.cc:1099-1140 fills
+ * options.ShardInfo, DBImpl_Sharding (db/db_impl_sharding.cpp:9-35) opens one
+ * DBImpl per shard, each with its own VersionSet, in a std::map<Slice, DBImpl*,
+ * cmpBySlice> keyed by the shard's UPPER bound, and every Get first runs
+ * Get_Target_Shard (db/db_impl_sharding.h:41-55): shards_pool.upper_bound(key);
+ * only then does Version::Get start (db_impl_sharding.cpp:92-99).
+ * readrandomshard is db_bench's read benchmark of this mode
+ * (db_bench.cc:1405-1434).  dlsm_shard_route_dev is that first step for a
+ * device-resident Get batch: each shard's Gets as one contiguous, aligned
+ * keyset plus the map back to the caller's Get indices, so that probe -> plan ->
+ * read -> advance runs per shard with the dlsm_version_* calls unchanged.
+ *
+ * The shard of a key is the number of upper bounds b with b <= key under
+ * Slice::compare (include/TimberSaw/slice.h:112-122: memcmp over the common
+ * length, then the shorter key first) -- std::map::upper_bound.  A key equal
+ * to a bound belongs to the NEXT shard; a bound that is a proper prefix of the
+ * key sorts below it.  A key at or past the last bound has no shard (the
+ * reference returns Corruption("Shard not found")): it goes to bin n_shards.
+ * Keys below the first shard's lower bound go to shard 0: the reference does
+ * not check lower bounds (its own TODO, db_impl_sharding.h:51).  With
+ * suffix_len = 8 the user key (ExtractUserKey) is compared and the whole
+ * internal key is moved.
+ *
+ * dlsm_shardmap_create: upper_bounds / lens in host memory, strictly ascending
+ * under that comparator, 1 <= n_shards <= DLSM_MAX_SHARDS, else DLSM_E_ARG.  An
+ * empty first bound is legal (shard 0 then holds nothing).
+ *
+ * dlsm_shard_route_dev, for bin s in 0 .. n_shards (device arrays):
+ *   shard_off_dev  u64[n_shards + 1]  the bin's first slot: the previous bin's
+ *                  end rounded up to DLSM_ROUTE_ALIGN (bin 0: 0)
+ *   shard_cnt_dev  u64[n_shards + 1]  the bin's Gets
+ *   gets_dev       u32[cap]  gets_dev[shard_off[s] .. shard_off[s] + shard_cnt[s])
+ *                  are the bin's Get indices in strictly ascending order; the
+ *                  slots in the gaps (and past the last run) are not written
+ *   keys_out_dev   cap * key_len bytes or NULL (fixed-stride keysets only): key
+ *                  gets_dev[p] copied whole to keys_out_dev + p * key_len.  With
+ *                  a 16-byte-aligned keys_out_dev and key_len % 4 == 0 every
+ *                  shard's run is then a 16-byte-aligned keyset -- what the
+ *                  LDS-staged key loaders of the probes need for 20-byte user
+ *                  keys and 28-byte internal keys; this is why runs are padded
+ *   cap            >= dlsm_shard_route_cap(n, n_shards)
+ * The result is a pure function of the inputs.  Variable-length keysets get the
+ * indices only: a non-NULL keys_out_dev with offsets != NULL is DLSM_E_ARG, and
+ * so are n > UINT32_MAX, a cap below dlsm_shard_route_cap and a map on another
+ * device.  n == 0 writes all-zero counts and offsets.  DLSM_OPT_FAULT_INJECT
+ * makes the call return the injected error (nothing is written).  Asynchronous
+ * on the context's stream: no host read-back, no synchronisation; the caller
+ * syncs and reads the two small arrays.
+ * dlsm_shard_route is the host-memory form (keys and outputs on the host,
+ * staged through device memory; the gap slots of gets / keys_out keep what
+ * they held).  Synchronous. */
+#define DLSM_MAX_SHARDS 511 /* + the "no shard" bin = 512 bins, one digit pass; the reference asserts < 256 */
+#define DLSM_ROUTE_ALIGN 4  /* every shard's run starts at a multiple of 4 keys */
+typedef struct dlsm_shardmap dlsm_shardmap; /* the shards' upper bounds, resident on a device */
+
+int dlsm_shardmap_create(dlsm_ctx* ctx, const uint8_t* const* upper_bounds, const uint64_t* lens, int n_shards,
+                         dlsm_shardmap** out);
+int dlsm_shardmap_destroy(dlsm_shardmap* map);
+int dlsm_shardmap_size(const dlsm_shardmap* map, int* n_shards);
+int dlsm_shard_route_dev(dlsm_ctx* ctx, const dlsm_shardmap* map, const dlsm_keyset* keys, uint64_t* shard_off_dev,
+                         uint64_t* shard_cnt_dev, uint32_t* gets_dev, uint8_t* keys_out_dev, uint64_t cap);
+int dlsm_shard_route(dlsm_ctx* ctx, const dlsm_shardmap* map, const dlsm_keyset* keys, uint64_t* shard_off,
+                     uint64_t* shard_cnt, uint32_t* gets, uint8_t* keys_out, uint64_t cap);
+/* n + (DLSM_ROUTE_ALIGN - 1) * (n_shards + 1), rounded up to DLSM_ROUTE_ALIGN. */
+uint64_t dlsm_shard_route_cap(uint64_t n, int n_shards);
+/* Gets per workgroup-chunk of the route's kernels (the sizes around which its
+ * tests are built). */
+uint32_t dlsm_shard_route_chunk(void);
+
 /* ---- legacy FilterPolicy format (util/bloom.cc) ------------------------- */
 
 /* CreateFilter(keys, n, dst) per job: writes bytes+1 bytes at out.

@@ -19,6 +19,8 @@
 //       StartBlock AddKey* ... Finish; public `result`
 //   FilterBlockReader       table/filter_block.h:70-85
 //       KeyMayMatch(block_offset, key) + KeysMayMatch (batch)
+//   ShardRouter             db/db_impl_sharding.h:41-55 (Get_Target_Shard over
+//       Options::ShardInfo): Shard (one key, host) + Route (a batch, GPU)
 //
 // Host types.  By default the header declares its own Slice and FilterPolicy
 // with the reference's surface.  Inside the reference tree, define
@@ -51,6 +53,7 @@
 #endif
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "dlsm_bloom.h"
@@ -1384,6 +1387,145 @@ class FilterBlockReader {
   }
   Slice contents_;
   dlsm_ctx* ctx_;
+};
+
+namespace host {
+
+// Slice::compare (include/TimberSaw/slice.h:112-122).
+inline int CompareBytes(const char* a, size_t an, const char* b, size_t bn) {
+  const size_t n = an < bn ? an : bn;
+  const int r = n ? memcmp(a, b, n) : 0;
+  if (r != 0) return r;
+  return an < bn ? -1 : (an > bn ? 1 : 0);
+}
+
+// shards_pool.upper_bound(key) (db/db_impl_sharding.h:41-55) over the sorted
+// upper bounds: the number of bounds <= key (uppers.size(): no shard).
+inline size_t UpperBoundShard(const std::vector<std::string>& uppers, const char* key, size_t len) {
+  size_t lo = 0, hi = uppers.size();
+  while (lo < hi) {
+    const size_t mid = lo + (hi - lo) / 2;
+    if (CompareBytes(uppers[mid].data(), uppers[mid].size(), key, len) <= 0) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// dlsm_shard_route's arrays from a host loop (host keyset; keys_out NULL or
+// fixed-length keys): counts, padded offsets, the ascending Get indices of every
+// bin and the keys' copies.  Slots in the gaps are not written.
+inline int RouteShards(const std::vector<std::string>& uppers, const dlsm_keyset& keys, uint64_t* shard_off,
+                       uint64_t* shard_cnt, uint32_t* gets, uint8_t* keys_out, uint64_t cap) {
+  const size_t bins = uppers.size() + 1;
+  if (uppers.empty() || uppers.size() > DLSM_MAX_SHARDS || !shard_off || !shard_cnt) return DLSM_E_ARG;
+  if (keys.n > 0xffffffffull || (keys.n && (!keys.bytes || !gets)) || (keys_out && keys.offsets)) return DLSM_E_ARG;
+  if (cap < dlsm_shard_route_cap(keys.n, static_cast<int>(uppers.size()))) return DLSM_E_ARG;
+  std::vector<uint16_t> bin(keys.n);
+  for (size_t s = 0; s < bins; s++) shard_cnt[s] = 0;
+  for (uint64_t g = 0; g < keys.n; g++) {
+    const uint64_t at = keys.offsets ? keys.offsets[g] : g * keys.key_len;
+    uint64_t len = keys.offsets ? keys.offsets[g + 1] - at : keys.key_len;
+    len = len > keys.suffix_len ? len - keys.suffix_len : 0;  // ExtractUserKey
+    bin[g] = static_cast<uint16_t>(UpperBoundShard(uppers, reinterpret_cast<const char*>(keys.bytes) + at, len));
+    shard_cnt[bin[g]]++;
+  }
+  uint64_t end = 0;
+  std::vector<uint64_t> next(bins);
+  for (size_t s = 0; s < bins; s++) {
+    shard_off[s] = next[s] = end;
+    end = (end + shard_cnt[s] + DLSM_ROUTE_ALIGN - 1) & ~static_cast<uint64_t>(DLSM_ROUTE_ALIGN - 1);
+  }
+  for (uint64_t g = 0; g < keys.n; g++) {
+    const uint64_t p = next[bin[g]]++;
+    gets[p] = static_cast<uint32_t>(g);
+    if (keys_out) memcpy(keys_out + p * keys.key_len, keys.bytes + g * keys.key_len, keys.key_len);
+  }
+  return DLSM_OK;
+}
+
+}  // namespace host
+
+// The first step of a sharded Get (DBImpl_Sharding, db/db_impl_sharding.cpp:
+// 9-35, 92-99): built from Options::ShardInfo's shape (options.h:189, [lower,
+// upper) per shard).  Like shards_pool the router keys the shards by their
+// upper bounds in Slice::compare order (a repeated upper bound keeps its first
+// entry); lower bounds are not checked (the reference's TODO,
+// db_impl_sharding.h:51).  Shard numbers are positions in that order;
+// InfoIndex maps one back to its ShardInfo entry.  Shard (one key, the per-Get
+// path) is answered on the host; Route (a batch in host memory) runs on the
+// GPU and, if the device cannot take it, in host::RouteShards with identical
+// arrays (counted: dlsm_fallback_note).
+class ShardRouter {
+ public:
+  typedef std::vector<std::pair<Slice, Slice>> ShardInfo;
+  explicit ShardRouter(const ShardInfo& shards, dlsm_ctx* ctx = nullptr) : ctx_(ctx) {
+    std::vector<std::pair<std::string, size_t>> ups;
+    for (size_t i = 0; i < shards.size(); i++)
+      ups.push_back(std::make_pair(std::string(shards[i].second.data(), shards[i].second.size()), i));
+    for (size_t i = 1; i < ups.size(); i++)  // insertion sort, stable: std::map keeps the first of equal keys
+      for (size_t j = i; j > 0 && host::CompareBytes(ups[j - 1].first.data(), ups[j - 1].first.size(),
+                                                     ups[j].first.data(), ups[j].first.size()) > 0; j--)
+        std::swap(ups[j - 1], ups[j]);
+    for (size_t i = 0; i < ups.size(); i++) {
+      if (i > 0 && ups[i].first == uppers_.back()) continue;
+      uppers_.push_back(ups[i].first);
+      index_.push_back(ups[i].second);
+    }
+  }
+  ~ShardRouter() {
+    if (map_) dlsm_shardmap_destroy(map_);
+  }
+  ShardRouter(const ShardRouter&) = delete;
+  ShardRouter& operator=(const ShardRouter&) = delete;
+
+  int n_shards() const { return static_cast<int>(uppers_.size()); }
+  size_t InfoIndex(int shard) const { return index_[static_cast<size_t>(shard)]; }
+  // Get_Target_Shard for one key (the user key): its shard, or -1 for the
+  // reference's "Shard not found".
+  int Shard(const Slice& key) const {
+    const size_t s = host::UpperBoundShard(uppers_, key.data(), key.size());
+    return s == uppers_.size() ? -1 : static_cast<int>(s);
+  }
+  static uint64_t Cap(uint64_t n, int n_shards) { return dlsm_shard_route_cap(n, n_shards); }
+  // dlsm_shard_route on host arrays: bin s (shard s; n_shards(): no shard) owns
+  // gets[shard_off[s] .. shard_off[s] + shard_cnt[s]).
+  int Route(const dlsm_keyset& keys, uint64_t* shard_off, uint64_t* shard_cnt, uint32_t* gets, uint8_t* keys_out,
+            uint64_t cap) {
+    dlsm_ctx* ctx = ctx_ ? ctx_ : ThreadContext();
+    last_status_ = ctx ? device_route(ctx, keys, shard_off, shard_cnt, gets, keys_out, cap) : DLSM_E_DEVICE;
+    if (last_status_ == DLSM_OK || last_status_ == DLSM_E_ARG) return last_status_;  // bad arguments stay bad
+    const int st = host::RouteShards(uppers_, keys, shard_off, shard_cnt, gets, keys_out, cap);
+    if (st == DLSM_OK) dlsm_fallback_note(ctx);
+    return st;
+  }
+  // The last Route's GPU status (the arrays are complete either way).
+  int status() const { return last_status_; }
+
+ private:
+  int device_route(dlsm_ctx* ctx, const dlsm_keyset& keys, uint64_t* shard_off, uint64_t* shard_cnt, uint32_t* gets,
+                   uint8_t* keys_out, uint64_t cap) {
+    if (uppers_.empty() || uppers_.size() > DLSM_MAX_SHARDS) return DLSM_E_ARG;
+    if (!map_ || map_device_ != dlsm_ctx_device(ctx)) {
+      if (map_) dlsm_shardmap_destroy(map_);
+      map_ = nullptr;
+      std::vector<const uint8_t*> p;
+      std::vector<uint64_t> l;
+      for (size_t i = 0; i < uppers_.size(); i++) {
+        p.push_back(reinterpret_cast<const uint8_t*>(uppers_[i].data()));
+        l.push_back(uppers_[i].size());
+      }
+      const int st = dlsm_shardmap_create(ctx, p.data(), l.data(), static_cast<int>(p.size()), &map_);
+      if (st != DLSM_OK) return st == DLSM_E_ARG ? DLSM_E_DEVICE : st;  // (the bounds are sorted and distinct)
+      map_device_ = dlsm_ctx_device(ctx);
+    }
+    return dlsm_shard_route(ctx, map_, &keys, shard_off, shard_cnt, gets, keys_out, cap);
+  }
+  std::vector<std::string> uppers_;
+  std::vector<size_t> index_;
+  dlsm_ctx* ctx_;
+  dlsm_shardmap* map_ = nullptr;
+  int map_device_ = -1;
+  int last_status_ = DLSM_OK;
 };
 
 }  // namespace dlsm_adapter
