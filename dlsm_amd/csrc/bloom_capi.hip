@@ -2443,7 +2443,7 @@ int dlsm_version_masks_advance_dev(dlsm_ctx* ctx, uint64_t* slot_mask_dev, const
 // ---------------------------------------------------------------------------
 // Shard route: DBImpl_Sharding::Get_Target_Shard for a Get batch
 // ---------------------------------------------------------------------------
-static_assert(DLSM_MAX_SHARDS == kRouteBins - 1 && DLSM_ROUTE_ALIGN == kRouteAlign, "shard route constants");
+static_assert(DLSM_MAX_SHARDS == kSortBins - 1 && DLSM_ROUTE_ALIGN == kRouteAlign, "shard route constants");
 
 struct dlsm_shardmap {
   int device = 0;
@@ -2516,7 +2516,7 @@ int dlsm_shard_route_dev(dlsm_ctx* ctx, const dlsm_shardmap* map, const dlsm_key
   const uint64_t n = keys->n;
   if (keys_out_dev && keys->offsets) return DLSM_E_ARG;  // variable-length keys: the indices only
   ShardRoute R;
-  DLSM_CHECK(plan_shard_route(n, map->n_shards, kRouteMaxWgs, R));
+  DLSM_CHECK(plan_shard_route(n, map->n_shards, kSortMaxWgs, R));
   if (cap < shard_route_cap(n, map->n_shards) || (n > 0 && !gets_dev)) return DLSM_E_ARG;
   if (ctx->fault) return -ctx->fault;
   DeviceGuard g(ctx->device);

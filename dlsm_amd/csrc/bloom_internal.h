@@ -352,8 +352,8 @@ struct ReadPlanDev {
   uint64_t n;
   uint32_t n_files;
   int32_t all;                 // DLSM_PLAN_ALL
-  uint32_t* cnt;               // u32[kPlanBins x table_wgs]
-  uint64_t* off;               // u64[kPlanBins x table_wgs]
+  uint32_t* cnt;               // u32[kSortBins x table_wgs]
+  uint64_t* off;               // u64[kSortBins x table_wgs]
   uint64_t* drop;              // u64[table_wgs]
   uint64_t* total;             // u64[1]
   uint64_t pair_items;         // items each keys / vals buffer holds

@@ -17,6 +17,20 @@ namespace plan {
 
 inline uint32_t ceil_div_u32(uint64_t a, uint64_t b) { return static_cast<uint32_t>((a + b - 1) / b); }
 
+// A workspace laid out region by region, every region 256-byte aligned.
+struct Layout {
+  uint64_t at = 0;  // the bytes so far
+  uint64_t take(uint64_t want) {
+    const uint64_t off = at;
+    at += (want + 255) & ~uint64_t(255);
+    return off;
+  }
+  void region(uint64_t* off, uint64_t* bytes, uint64_t want) {
+    *off = take(want);
+    *bytes = want;
+  }
+};
+
 inline KeyDesc to_desc(const dlsm_keyset& k) {
   KeyDesc d;
   d.bytes = k.bytes;
@@ -731,15 +745,11 @@ inline int plan_version(const dlsm_version_file* files, int n_files, const uint8
 // ---- read plan (read_plan.hip) ---------------------------------------------------
 // One digit pass of the plan's counting sort: its items (pass 0: the n Gets;
 // later passes: the tasks, of which the host knows only the bound items_max --
-// the kernels clip to the device-side total) are cut into chunks of kPlanChunk,
-// cpw chunks per workgroup, so that at most kPlanMaxWgs workgroups share the
-// (bin, workgroup) count table whatever n is.
-struct ReadPlanPass {
+// the kernels clip to the device-side total) on sort_grid's grid of kPlanChunk
+// chunks.
+struct ReadPlanPass : SortGrid {
   uint64_t items_max = 0;
-  uint64_t chunks = 0;
-  uint32_t cpw = 1;   // chunks per workgroup
-  uint32_t nwg = 0;   // workgroups (the grid); 0: nothing to do
-  uint32_t shift = 0; // the digit's first bit
+  uint32_t shift = 0;  // the digit's first bit
 };
 
 // Everything dlsm_version_read_plan_dev computes before it launches: the
@@ -753,7 +763,7 @@ struct ReadPlan {
   uint64_t tasks_max = 0;                // bound on the tasks: n (FIRST) or n x tasks_per_get (ALL)
   ReadPlanPass pass[kPlanMaxPasses];
   uint32_t table_wgs = 1;    // workgroup rows of the tables: max nwg over the passes
-  uint64_t table_entries = 0;  // kPlanBins x table_wgs
+  uint64_t table_entries = 0;  // kSortBins x table_wgs
   uint64_t pair_items = 0;   // items of each keys / vals buffer in use
   uint64_t cnt_off = 0, cnt_bytes = 0;    // u32[table_entries]: per (bin, workgroup) counts
   uint64_t off_off = 0, off_bytes = 0;    // u64[table_entries]: their exclusive prefix sums
@@ -768,16 +778,14 @@ struct ReadPlan {
 inline int read_plan_passes(uint64_t n_files) {
   int bits = 0;
   while (n_files > 1 && ((n_files - 1) >> bits) != 0) bits++;
-  return std::max(1, (bits + kPlanDigitLg - 1) / kPlanDigitLg);
+  return std::max(1, (bits + kSortBinLg - 1) / kSortBinLg);
 }
 
 inline ReadPlanPass read_plan_pass(uint64_t items_max, uint32_t shift) {
   ReadPlanPass p;
   p.items_max = items_max;
   p.shift = shift;
-  p.chunks = (items_max + kPlanChunk - 1) / kPlanChunk;
-  p.cpw = static_cast<uint32_t>(std::max<uint64_t>(1, (p.chunks + kPlanMaxWgs - 1) / kPlanMaxWgs));
-  p.nwg = static_cast<uint32_t>((p.chunks + p.cpw - 1) / p.cpw);
+  static_cast<SortGrid&>(p) = sort_grid(items_max, kPlanChunk, kSortMaxWgs);
   return p;
 }
 
@@ -791,30 +799,24 @@ inline int plan_read(uint64_t n, uint64_t n_files, uint32_t tasks_per_get, int m
   R.passes = read_plan_passes(n_files);
   R.tasks_max = mode == DLSM_PLAN_FIRST ? n : n * tasks_per_get;
   R.pass[0] = read_plan_pass(n, 0);
-  for (int p = 1; p < R.passes; p++) R.pass[p] = read_plan_pass(R.tasks_max, static_cast<uint32_t>(p) * kPlanDigitLg);
+  for (int p = 1; p < R.passes; p++) R.pass[p] = read_plan_pass(R.tasks_max, static_cast<uint32_t>(p) * kSortBinLg);
   for (int p = 0; p < R.passes; p++) R.table_wgs = std::max(R.table_wgs, R.pass[p].nwg);
-  R.table_entries = static_cast<uint64_t>(kPlanBins) * R.table_wgs;
-  auto pad = [](uint64_t b) { return (b + 255) & ~uint64_t(255); };
-  uint64_t at = 0;
-  auto region = [&](uint64_t* off, uint64_t* bytes, uint64_t want) {
-    *off = at;
-    *bytes = want;
-    at += pad(want);
-  };
-  region(&R.cnt_off, &R.cnt_bytes, sizeof(uint32_t) * R.table_entries);
-  region(&R.off_off, &R.off_bytes, sizeof(uint64_t) * R.table_entries);
-  region(&R.drop_off, &R.drop_bytes, sizeof(uint64_t) * R.table_wgs);
-  region(&R.total_off, &R.total_bytes, sizeof(uint64_t));
+  R.table_entries = static_cast<uint64_t>(kSortBins) * R.table_wgs;
+  Layout ws;
+  ws.region(&R.cnt_off, &R.cnt_bytes, sizeof(uint32_t) * R.table_entries);
+  ws.region(&R.off_off, &R.off_bytes, sizeof(uint64_t) * R.table_entries);
+  ws.region(&R.drop_off, &R.drop_bytes, sizeof(uint64_t) * R.table_wgs);
+  ws.region(&R.total_off, &R.total_bytes, sizeof(uint64_t));
   // keys[1]: FIRST's per-Get file ids, and pass 1's output; the rest only for
   // several passes (vals[1]: written by pass 1 when a pass 2 reads it)
   const bool multi = R.passes > 1;
   R.pair_items = R.tasks_max;
   const uint64_t pb = sizeof(uint32_t) * R.pair_items;
-  region(&R.keys_off[0], &R.keys_bytes[0], multi ? pb : 0);
-  region(&R.vals_off[0], &R.vals_bytes[0], multi ? pb : 0);
-  region(&R.keys_off[1], &R.keys_bytes[1], (multi || mode == DLSM_PLAN_FIRST) ? pb : 0);
-  region(&R.vals_off[1], &R.vals_bytes[1], R.passes > 2 ? pb : 0);
-  R.bytes = at;
+  ws.region(&R.keys_off[0], &R.keys_bytes[0], multi ? pb : 0);
+  ws.region(&R.vals_off[0], &R.vals_bytes[0], multi ? pb : 0);
+  ws.region(&R.keys_off[1], &R.keys_bytes[1], (multi || mode == DLSM_PLAN_FIRST) ? pb : 0);
+  ws.region(&R.vals_off[1], &R.vals_bytes[1], R.passes > 2 ? pb : 0);
+  R.bytes = ws.at;
   return DLSM_OK;
 }
 
@@ -838,15 +840,11 @@ inline uint32_t plan_tasks_per_get(const PlanShape& s) {
 }
 
 // ---- shard route (shard_route.hip) -----------------------------------------------
-// The route's one counting-sort pass: the n Gets cut into chunks of kRouteChunk,
-// cpw chunks per workgroup, so that at most max_wgs (the ABI: kRouteMaxWgs)
-// workgroups share the (bin, workgroup) count table whatever n is; and the
-// workspace layout (byte offsets, every region 256-byte aligned).
-struct ShardRoute {
+// The route's one counting-sort pass: the n Gets on sort_grid's grid of
+// kRouteChunk chunks and at most max_wgs (the ABI: kSortMaxWgs) workgroups, and
+// the workspace layout (byte offsets, every region 256-byte aligned).
+struct ShardRoute : SortGrid {
   uint32_t bins = 0;     // n_shards + 1: the shards and the "no shard" bin
-  uint64_t chunks = 0;
-  uint32_t cpw = 1;      // chunks per workgroup
-  uint32_t nwg = 0;      // workgroups (the grid); 0: nothing to do
   uint64_t table_entries = 0;               // bins x nwg
   uint64_t ids_off = 0, ids_bytes = 0;      // u16[n]: every Get's bin (the count pass writes them)
   uint64_t cnt_off = 0, cnt_bytes = 0;      // u32[table_entries]: per (bin, workgroup) counts
@@ -873,25 +871,17 @@ inline uint64_t shard_route_offsets(const uint64_t* cnt, uint32_t bins, uint64_t
 }
 
 inline int plan_shard_route(uint64_t n, int n_shards, uint32_t max_wgs, ShardRoute& R) {
-  if (n > 0xffffffffull || n_shards < 1 || n_shards > static_cast<int>(kRouteBins) - 1 || max_wgs == 0)
+  if (n > 0xffffffffull || n_shards < 1 || n_shards > static_cast<int>(kSortBins) - 1 || max_wgs == 0)
     return DLSM_E_ARG;
   R = ShardRoute();
   R.bins = static_cast<uint32_t>(n_shards) + 1;
-  R.chunks = (n + kRouteChunk - 1) / kRouteChunk;
-  R.cpw = static_cast<uint32_t>(std::max<uint64_t>(1, (R.chunks + max_wgs - 1) / max_wgs));
-  R.nwg = static_cast<uint32_t>((R.chunks + R.cpw - 1) / R.cpw);
+  static_cast<SortGrid&>(R) = sort_grid(n, kRouteChunk, max_wgs);
   R.table_entries = static_cast<uint64_t>(R.bins) * R.nwg;
-  auto pad = [](uint64_t b) { return (b + 255) & ~uint64_t(255); };
-  uint64_t at = 0;
-  auto region = [&](uint64_t* off, uint64_t* bytes, uint64_t want) {
-    *off = at;
-    *bytes = want;
-    at += pad(want);
-  };
-  region(&R.ids_off, &R.ids_bytes, sizeof(uint16_t) * n);
-  region(&R.cnt_off, &R.cnt_bytes, sizeof(uint32_t) * R.table_entries);
-  region(&R.off_off, &R.off_bytes, sizeof(uint64_t) * R.table_entries);
-  R.bytes = at;
+  Layout ws;
+  ws.region(&R.ids_off, &R.ids_bytes, sizeof(uint16_t) * n);
+  ws.region(&R.cnt_off, &R.cnt_bytes, sizeof(uint32_t) * R.table_entries);
+  ws.region(&R.off_off, &R.off_bytes, sizeof(uint64_t) * R.table_entries);
+  R.bytes = ws.at;
   return DLSM_OK;
 }
 
@@ -906,7 +896,7 @@ struct ShardMapImage {
 };
 
 inline int plan_shardmap(const uint8_t* const* bounds, const uint64_t* lens, int n_shards, ShardMapImage& M) {
-  if (!bounds || !lens || n_shards < 1 || n_shards > static_cast<int>(kRouteBins) - 1) return DLSM_E_ARG;
+  if (!bounds || !lens || n_shards < 1 || n_shards > static_cast<int>(kSortBins) - 1) return DLSM_E_ARG;
   M = ShardMapImage();
   M.off.assign(1, 0);
   for (int i = 0; i < n_shards; i++) {
@@ -916,11 +906,11 @@ inline int plan_shardmap(const uint8_t* const* bounds, const uint64_t* lens, int
     if (lens[i]) M.bytes.insert(M.bytes.end(), bounds[i], bounds[i] + lens[i]);
     M.off.push_back(M.bytes.size());
   }
-  auto pad = [](uint64_t b) { return (b + 255) & ~uint64_t(255); };
-  M.pre_off = 0;
-  M.off_off = pad(sizeof(RoutePrefix) * M.pre.size());
-  M.bytes_off = M.off_off + pad(sizeof(uint64_t) * M.off.size());
-  M.total = M.bytes_off + pad(std::max<size_t>(1, M.bytes.size()));
+  Layout img;
+  M.pre_off = img.take(sizeof(RoutePrefix) * M.pre.size());
+  M.off_off = img.take(sizeof(uint64_t) * M.off.size());
+  M.bytes_off = img.take(std::max<size_t>(1, M.bytes.size()));
+  M.total = img.at;
   return DLSM_OK;
 }
 

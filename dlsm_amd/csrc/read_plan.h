@@ -5,27 +5,22 @@
 #include <stdint.h>
 
 #include "bloom_math.h"
+#include "sort_pass.h"
 
 namespace dlsm {
 
 // The plan is a stable counting sort of (Get, file) tasks by file id, one digit
-// of kPlanDigitLg bits per pass, least significant first.
-constexpr int kPlanDigitLg = 9;
-constexpr uint32_t kPlanBins = 1u << kPlanDigitLg;  // digit bins (LDS): one pass up to 512 files
-constexpr int kPlanBlock = 1024;                    // threads per histogram / scatter workgroup (two per CU)
-constexpr int kPlanWaves = kPlanBlock / 64;
+// of kSortBinLg bits per pass (sort_pass.h), least significant first: one pass
+// up to kSortBins files.
 constexpr int kPlanChunkLg = 15;
 constexpr uint32_t kPlanChunk = 1u << kPlanChunkLg;  // items (Gets or tasks) per workgroup-chunk
-constexpr uint32_t kPlanWaveItems = kPlanChunk / kPlanWaves;  // a wave's contiguous share of a chunk
-constexpr uint32_t kPlanMaxWgs = 512;       // workgroups per pass: rows of the (bin, workgroup) table
+constexpr uint32_t kPlanWaveItems = kPlanChunk / kSortWaves;  // a wave's contiguous share of a chunk
 constexpr int kPlanMaxPasses = 4;           // 4 x 9 bits >= the 31 bits of an int file count
-constexpr int kPlanScanBlock = 1024;        // the scan's single workgroup
 constexpr uint32_t kPlanNoFile = 0xffffffffu;  // decoder: the task is dropped; a Get without a task
 constexpr int kPlanLevels = 5;              // levels 1 .. kNumLevels-1: one search slot each
 
 static_assert(kPlanWaveItems % 128 == 0, "a wave walks its share 128 Gets (one 16-byte load per lane) at a time");
-static_assert(kPlanBins <= kPlanBlock, "scatter: thread d < kPlanBins owns bin d");
-static_assert(kPlanDigitLg * kPlanMaxPasses >= 31, "the passes cover every file count an int holds");
+static_assert(kSortBinLg * kPlanMaxPasses >= 31, "the passes cover every file count an int holds");
 
 // What the decoder needs of a version: its search slots and, per level 1..5,
 // where the level's files start in search order and how many there are.
@@ -49,6 +44,6 @@ DLSM_HD uint32_t plan_task_file(const PlanShape& v, uint32_t slot, uint32_t pick
 }
 
 // The digit of file id f that pass p sorts by.
-DLSM_HD uint32_t plan_digit(uint32_t f, uint32_t shift) { return (f >> shift) & (kPlanBins - 1u); }
+DLSM_HD uint32_t plan_digit(uint32_t f, uint32_t shift) { return (f >> shift) & (kSortBins - 1u); }
 
 }  // namespace dlsm

@@ -2,27 +2,16 @@
 // (dlsm_version_read_plan_dev): the version probe's answers grouped by file.
 //
 // A stable counting sort of the (Get, file) tasks by the caller's file index,
-// kPlanDigitLg bits per pass, least significant digit first, the digit's bins
-// in LDS.  Per pass three launches, ordered by the stream alone (no counter is
-// shared between workgroups, nothing inside a launch waits for another
-// workgroup):
-//   histogram  workgroup w walks its cpw chunks of kPlanChunk items and writes
-//              its count per bin to cnt[bin * nwg + w];
-//   scan       one workgroup turns cnt into exclusive prefix sums off[] in that
-//              (bin-major, then workgroup) order -- the first output position of
-//              every (bin, workgroup) -- and, when one pass covers the files,
-//              file_begin;
-//   scatter    workgroup w walks the same items again and writes each to
-//              off[bin * nwg + w] + (its rank among w's items of that bin).
-// Ranks follow item order, never the arrival order of atomics: inside a wave
-// by ballots over the digit's bits (the lanes with the same digit are the AND
-// over the bits of bit ? ballot : ~ballot; the rank is the count of those
-// below), across waves by the wave's number (each wave owns a contiguous share
-// of the chunk and a row of LDS counts), across chunks and workgroups by the
-// tables.  Items are in ascending Get order in pass 0 and every pass is stable,
-// so each file's Gets come out strictly ascending.  Workgroups have 1,024
-// threads, two per CU: at most kPlanMaxWgs of them share the tables, so the
-// waves a CU needs to hide the loads have to come from inside a workgroup.
+// one pass of sort_pass.h per digit of kSortBinLg bits, least significant
+// first.  Items are in ascending Get order in pass 0 and every pass is stable,
+// so each file's Gets come out strictly ascending.  The histogram of pass 0
+// also counts the dropped tasks; the scan writes file_begin when one pass
+// covers the files (bin == file), else plan_bounds_kernel finds it in the
+// sorted ids.
+//
+// Sources of a pass: the masks and picks (pass 0; ALL in both launches), the
+// per-Get file ids the histogram leaves (pass 0, FIRST: the scatter), the
+// pairs of the pass before (later passes).
 //
 // Bytes per Get, DLSM_PLAN_FIRST, one pass (db_bench's 426 files): the
 // histogram reads the 8-B mask (16-byte loads) and, for a task on levels 1-5
@@ -32,8 +21,7 @@
 // against 8 + 4 B twice without the id array.  DLSM_PLAN_ALL decodes the masks
 // and picks in both launches (a Get has several tasks: 2 x (8 B + picks) +
 // 4 B per task).  Every further pass reads 4 B (histogram) + 8 B (scatter) and
-// writes 8 B per task.  The tables are kPlanBins x nwg <= 512 x 512 entries
-// (1 MiB of counts, 2 MiB of offsets) whatever n is.
+// writes 8 B per task.
 #include <hip/hip_runtime.h>
 
 #include "bloom_internal.h"
@@ -51,27 +39,11 @@ struct PlanPassDev {
 
 enum : int { kSrcMasks = 0, kSrcIds = 1, kSrcPairs = 2 };
 
-static_assert(kPlanBlock == 64 * kPlanWaves, "wave64");
-static_assert(static_cast<uint64_t>(kPlanBins) * kPlanMaxWgs <= 0xffffffffull / 4, "table index in u32");
-static_assert(kPlanBins % 4 == 0, "the scan loads four counts (16 B) per thread");
-static_assert(kPlanScanBlock == 1024 && kPlanScanBlock / 64 == 16, "scan: sixteen waves");
-
-__device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
-  return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
-}
-
 // The active lanes of the wave whose digit equals this lane's.  same: the
 // caller knows that every active lane holds one file (a level-0 slot).
 __device__ __forceinline__ uint64_t plan_peers(uint32_t d, bool active, bool same) {
-  uint64_t peers = __ballot(active);
-  if (same) return peers;
-#pragma unroll
-  for (int b = 0; b < kPlanDigitLg; b++) {
-    const bool bit = (d >> b) & 1u;
-    const uint64_t bb = __ballot(bit);
-    peers &= bit ? bb : ~bb;
-  }
-  return peers;
+  const uint64_t among = __ballot(active);
+  return same ? among : digit_peers(among, d, kSortBinLg);
 }
 
 // Task (Get g, slot s) -> the caller's file index, or kPlanNoFile (dropped).
@@ -188,51 +160,50 @@ __device__ __forceinline__ uint64_t pass_items(const ReadPlanDev& a) {
 // (pass 0) it also counts the dropped tasks and, in FIRST mode, writes each
 // Get's file id (kPlanNoFile: none) for the scatter.
 template <int SRC, bool ALL>
-__global__ __launch_bounds__(kPlanBlock, 8) void plan_hist_kernel(ReadPlanDev a, PlanPassDev p) {
-  __shared__ uint32_t hist[kPlanBins];
+__global__ __launch_bounds__(kSortBlock, 8) void plan_hist_kernel(ReadPlanDev a, PlanPassDev p) {
+  __shared__ uint32_t hist[kSortBins];
   __shared__ unsigned long long sdrop;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint32_t w = blockIdx.x;
-  for (uint32_t d = tid; d < kPlanBins; d += kPlanBlock) hist[d] = 0;
+  for (uint32_t d = tid; d < kSortBins; d += kSortBlock) hist[d] = 0;
   if (tid == 0) sdrop = 0;
   __syncthreads();
   const uint64_t items = pass_items<SRC>(a);
   uint64_t dropped = 0;
   auto count = [&](uint32_t key, uint32_t val, bool ok, bool same) {
     const bool active = key != kPlanNoFile;
-    const uint32_t d = plan_digit(key, p.shift);  // < kPlanBins
+    const uint32_t d = plan_digit(key, p.shift);  // < kSortBins
     const uint64_t peers = plan_peers(d, active, same);
-    if (active && lanes_below(peers) == 0) atomicAdd(&hist[d], static_cast<uint32_t>(__builtin_popcountll(peers)));
+    hist_add(hist, d, active, peers);
     if (SRC == kSrcMasks && !ALL && ok) p.keys_in[val] = key;  // val = the Get, < n
   };
   for (uint64_t c = static_cast<uint64_t>(w) * p.cpw; c < static_cast<uint64_t>(w + 1) * p.cpw; c++) {
     const uint64_t c0 = c * kPlanChunk;
     if (c0 >= items) break;
-    const uint64_t i0 = c0 + static_cast<uint64_t>(wave) * kPlanWaveItems;
-    const uint64_t i1 = i0 + kPlanWaveItems < items ? i0 + kPlanWaveItems : items;
-    walk<SRC, ALL>(a, p, i0, i1, lane, dropped, count);
+    const WaveShare sh = wave_share<kPlanChunk>(c0, wave, items);
+    walk<SRC, ALL>(a, p, sh.i0, sh.i1, lane, dropped, count);
   }
   if (SRC == kSrcMasks) {
     for (int d = 32; d > 0; d >>= 1) dropped += __shfl_xor(dropped, d, 64);
     if (lane == 0 && dropped) atomicAdd(&sdrop, static_cast<unsigned long long>(dropped));
   }
   __syncthreads();
-  for (uint32_t d = tid; d < kPlanBins; d += kPlanBlock) a.cnt[d * p.nwg + w] = hist[d];  // < kPlanBins * nwg
+  hist_flush(hist, kSortBins, a.cnt, p.nwg, w, tid);
   if (SRC == kSrcMasks && tid == 0) a.drop[w] = sdrop;
 }
 
-// Scan: off[] = exclusive prefix sums of cnt[0, kPlanBins * nwg); *total; with
+// Scan: off[] = exclusive prefix sums of cnt[0, kSortBins * nwg); *total; with
 // write_begin (one pass covers the files: bin == file) file_begin; with
 // write_drop the sum of the workgroups' dropped tasks.
-__global__ __launch_bounds__(kPlanScanBlock) void plan_scan_kernel(ReadPlanDev a, uint32_t nwg, int write_begin,
+__global__ __launch_bounds__(kSortScanBlock) void plan_scan_kernel(ReadPlanDev a, uint32_t nwg, int write_begin,
                                                                    int write_drop) {
-  __shared__ uint64_t wsum[kPlanScanBlock / 64];
+  __shared__ uint64_t wsum[kSortScanBlock / 64];
   constexpr uint32_t kPer = 16;  // entries per thread and tile: four 16-byte loads in flight
-  static_assert(kPlanBins % kPer == 0, "a tile never ends inside a thread's entries");
+  static_assert(kSortBins % kPer == 0, "a tile never ends inside a thread's entries");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint32_t entries = kPlanBins * nwg;  // a multiple of kPer
+  const uint32_t entries = kSortBins * nwg;  // a multiple of kPer
   uint64_t carry = 0;
-  for (uint32_t base = 0; base < entries; base += kPer * kPlanScanBlock) {
+  for (uint32_t base = 0; base < entries; base += kPer * kSortScanBlock) {
     const uint32_t e = base + kPer * tid;
     uint32_t c[kPer];
 #pragma unroll
@@ -252,7 +223,7 @@ __global__ __launch_bounds__(kPlanScanBlock) void plan_scan_kernel(ReadPlanDev a
     if (lane == 63) wsum[wave] = inc;
     __syncthreads();
     uint64_t wpre = 0, tile = 0;
-    for (int k = 0; k < kPlanScanBlock / 64; k++) {
+    for (int k = 0; k < kSortScanBlock / 64; k++) {
       const uint64_t v = wsum[k];
       if (k < wave) wpre += v;
       tile += v;
@@ -280,35 +251,32 @@ __global__ __launch_bounds__(kPlanScanBlock) void plan_scan_kernel(ReadPlanDev a
   }
   if (write_drop && a.dropped) {
     uint64_t d = 0;
-    for (uint32_t q = tid; q < nwg; q += kPlanScanBlock) d += a.drop[q];
+    for (uint32_t q = tid; q < nwg; q += kSortScanBlock) d += a.drop[q];
     for (int k = 32; k > 0; k >>= 1) d += __shfl_xor(d, k, 64);
     if (lane == 0) wsum[wave] = d;
     __syncthreads();
     if (tid == 0) {
       uint64_t t = 0;
-      for (int k = 0; k < kPlanScanBlock / 64; k++) t += wsum[k];
+      for (int k = 0; k < kSortScanBlock / 64; k++) t += wsum[k];
       *a.dropped = t;
     }
   }
 }
 
-// Scatter: every item to off[bin * nwg + w] + its rank among workgroup w's
-// items of the bin.  Per chunk: (A) each wave counts its share per bin into
-// its own LDS row, (B) thread d turns bin d's wave counts into the waves' start
-// positions inside the chunk (the chunk's own start after the chunks before is
-// kept in its register), (C) each wave walks its share again and places the
-// items.
+// Scatter (sort_pass.h, (A) to (C)).  From the masks (A) counts each wave's
+// share per bin and (C) walks the share again, ranking as it places; items from
+// an array are ranked once and held.
 template <int SRC, bool ALL, bool LAST>
-__global__ __launch_bounds__(kPlanBlock, 8) void plan_scatter_kernel(ReadPlanDev a, PlanPassDev p) {
-  __shared__ uint32_t cnt[kPlanWaves][kPlanBins];  // (A) a wave's items per bin; zero between chunks
-  __shared__ uint32_t off[kPlanWaves][kPlanBins];  // (C) the wave's next position in the bin, from start[]
-  __shared__ uint64_t start[kPlanBins];            // the chunk's first position per bin
+__global__ __launch_bounds__(kSortBlock, 8) void plan_scatter_kernel(ReadPlanDev a, PlanPassDev p) {
+  __shared__ uint32_t cnt[kSortWaves][kSortBins];  // (A) a wave's items per bin; zero between chunks
+  __shared__ uint32_t off[kSortWaves][kSortBins];  // (C) the wave's next position in the bin, from start[]
+  __shared__ uint64_t start[kSortBins];            // the chunk's first position per bin
   static_assert(sizeof(cnt) + sizeof(off) + sizeof(start) <= 80 * 1024, "scatter LDS: two workgroups per CU");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint32_t w = blockIdx.x;
-  uint64_t next = 0;  // thread d < kPlanBins: bin d's first position of the next chunk
-  if (tid < static_cast<int>(kPlanBins)) next = a.off[static_cast<uint32_t>(tid) * p.nwg + w];
-  for (uint32_t q = tid; q < kPlanWaves * kPlanBins; q += kPlanBlock) (&cnt[0][0])[q] = 0;
+  uint64_t next = 0;  // thread d < kSortBins: bin d's first position of the next chunk
+  if (tid < static_cast<int>(kSortBins)) next = a.off[static_cast<uint32_t>(tid) * p.nwg + w];
+  for (uint32_t q = tid; q < kSortWaves * kSortBins; q += kSortBlock) (&cnt[0][0])[q] = 0;
   __syncthreads();
   const uint64_t items = pass_items<SRC>(a);
   uint64_t unused = 0;
@@ -339,9 +307,9 @@ __global__ __launch_bounds__(kPlanBlock, 8) void plan_scatter_kernel(ReadPlanDev
     }
   };
   auto spread = [&]() {  // (B)
-    if (tid < static_cast<int>(kPlanBins)) {
+    if (tid < static_cast<int>(kSortBins)) {
       uint32_t run = 0;  // <= kPlanChunk x 64 tasks
-      for (int v = 0; v < kPlanWaves; v++) {
+      for (int v = 0; v < kSortWaves; v++) {
         const uint32_t t = cnt[v][tid];
         cnt[v][tid] = 0;
         off[v][tid] = run;
@@ -356,9 +324,9 @@ __global__ __launch_bounds__(kPlanBlock, 8) void plan_scatter_kernel(ReadPlanDev
     // registers as (digit, rank inside the wave's share) between (A) and (C),
     // so (C) neither reads them again nor repeats the ballots.
     constexpr int kHold = 8;
-    constexpr uint32_t kSub = kHold * 64u * kPlanWaves;  // items per sub-chunk
+    constexpr uint32_t kSub = kHold * 64u * kSortWaves;  // items per sub-chunk
     static_assert(kPlanChunk % kSub == 0, "sub-chunks tile the workgroup's chunks");
-    static_assert(kHold * 64u <= (1u << (32 - kPlanDigitLg)) - 1u, "rank and digit share a register");
+    static_assert(kHold * 64u <= (1u << (32 - kSortBinLg)) - 1u, "rank and digit share a register");
     const uint64_t w0 = static_cast<uint64_t>(w) * p.cpw * kPlanChunk;
     uint64_t w1 = w0 + static_cast<uint64_t>(p.cpw) * kPlanChunk;
     if (w1 > items) w1 = items;
@@ -369,25 +337,18 @@ __global__ __launch_bounds__(kPlanBlock, 8) void plan_scatter_kernel(ReadPlanDev
       for (int q = 0; q < kHold; q++) {
         const uint64_t j = i0 + 64u * q + lane;
         const uint32_t key = j < w1 ? p.keys_in[j] : kPlanNoFile;
-        const bool active = key != kPlanNoFile;
         const uint32_t d = plan_digit(key, p.shift);
-        const uint64_t peers = plan_peers(d, active, false);
-        const uint32_t below = lanes_below(peers);
-        const uint32_t loc = active ? cnt[wave][d] + below : 0;
-        __builtin_amdgcn_wave_barrier();
-        if (active && below == 0) cnt[wave][d] = loc + static_cast<uint32_t>(__builtin_popcountll(peers));
-        __builtin_amdgcn_wave_barrier();
-        held[q] = active ? (d | (loc << kPlanDigitLg)) : kPlanNoFile;
+        const bool active = key != kPlanNoFile;
+        held[q] = rank_held(cnt[wave], d, active, plan_peers(d, active, false));
       }
       __syncthreads();
       spread();
       __syncthreads();
 #pragma unroll
       for (int q = 0; q < kHold; q++) {
-        if (held[q] == kPlanNoFile) continue;
+        if (held[q] == kSortNoItem) continue;
         const uint64_t j = i0 + 64u * q + lane;
-        const uint32_t d = held[q] & (kPlanBins - 1u);
-        const uint64_t pos = start[d] + off[wave][d] + (held[q] >> kPlanDigitLg);
+        const uint64_t pos = held_pos(held[q], off[wave], start);
         const uint32_t val = SRC == kSrcPairs ? p.vals_in[j] : static_cast<uint32_t>(j);
         if (LAST) {
           if (pos < a.cap) a.gets[pos] = val;
@@ -403,13 +364,12 @@ __global__ __launch_bounds__(kPlanBlock, 8) void plan_scatter_kernel(ReadPlanDev
   for (uint64_t c = static_cast<uint64_t>(w) * p.cpw; c < static_cast<uint64_t>(w + 1) * p.cpw; c++) {
     const uint64_t c0 = c * kPlanChunk;
     if (c0 >= items) break;
-    const uint64_t i0 = c0 + static_cast<uint64_t>(wave) * kPlanWaveItems;
-    const uint64_t i1 = i0 + kPlanWaveItems < items ? i0 + kPlanWaveItems : items;
-    walk<SRC, ALL>(a, p, i0, i1, lane, unused, count);
+    const WaveShare sh = wave_share<kPlanChunk>(c0, wave, items);
+    walk<SRC, ALL>(a, p, sh.i0, sh.i1, lane, unused, count);
     __syncthreads();
     spread();
     __syncthreads();
-    walk<SRC, ALL>(a, p, i0, i1, lane, unused, place);
+    walk<SRC, ALL>(a, p, sh.i0, sh.i1, lane, unused, place);
   }
 }
 
@@ -451,17 +411,17 @@ __global__ __launch_bounds__(kBlock) void masks_advance_kernel(uint64_t* mask, c
 hipError_t launch_read_plan_pass(const ReadPlanDev& a, int pass, int passes, uint32_t shift, uint32_t cpw,
                                  uint32_t nwg, uint32_t* keys_in, const uint32_t* vals_in, uint32_t* keys_out,
                                  uint32_t* vals_out, hipStream_t s) {
-  if (nwg == 0 || nwg > kPlanMaxWgs || cpw == 0) return hipErrorInvalidValue;
+  if (nwg == 0 || nwg > kSortMaxWgs || cpw == 0) return hipErrorInvalidValue;
   const PlanPassDev p{shift, cpw, nwg, keys_in, vals_in, keys_out, vals_out};
   const bool last = pass + 1 == passes;
-  const dim3 grid(nwg), block(kPlanBlock);
+  const dim3 grid(nwg), block(kSortBlock);
   if (pass == 0) {
     if (a.all) hipLaunchKernelGGL((plan_hist_kernel<kSrcMasks, true>), grid, block, 0, s, a, p);
     else hipLaunchKernelGGL((plan_hist_kernel<kSrcMasks, false>), grid, block, 0, s, a, p);
   } else {
     hipLaunchKernelGGL((plan_hist_kernel<kSrcPairs, false>), grid, block, 0, s, a, p);
   }
-  hipLaunchKernelGGL(plan_scan_kernel, dim3(1), dim3(kPlanScanBlock), 0, s, a, nwg, passes == 1 ? 1 : 0,
+  hipLaunchKernelGGL(plan_scan_kernel, dim3(1), dim3(kSortScanBlock), 0, s, a, nwg, passes == 1 ? 1 : 0,
                      pass == 0 ? 1 : 0);
 #define DLSM_PLAN_SCATTER(SRC, ALL)                                                                   \
   do {                                                                                                \

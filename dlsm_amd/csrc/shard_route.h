@@ -6,27 +6,22 @@
 #include <stdint.h>
 
 #include "bloom_math.h"
+#include "sort_pass.h"
 
 namespace dlsm {
 
-// The route is one stable counting-sort pass of the Gets by shard: the bins are
-// the shards plus the "no shard" bin, all in one digit (LDS).
-constexpr int kRouteBinLg = 9;
-constexpr uint32_t kRouteBins = 1u << kRouteBinLg;    // n_shards + 1 <= 512 (DLSM_MAX_SHARDS = 511)
-constexpr int kRouteBlock = 1024;                     // threads per count / scatter workgroup (two per CU)
-constexpr int kRouteWaves = kRouteBlock / 64;
+// The route is one stable counting-sort pass (sort_pass.h) of the Gets by shard:
+// the bins are the shards plus the "no shard" bin, n_shards + 1 <= kSortBins
+// (DLSM_MAX_SHARDS = 511).
 constexpr int kRouteChunkLg = 13;
 constexpr uint32_t kRouteChunk = 1u << kRouteChunkLg;  // Gets per workgroup-chunk
-constexpr uint32_t kRouteWaveItems = kRouteChunk / kRouteWaves;  // a wave's contiguous share of a chunk
+constexpr uint32_t kRouteWaveItems = kRouteChunk / kSortWaves;  // a wave's contiguous share of a chunk
 constexpr int kRouteHold = kRouteWaveItems / 64;      // Gets a lane holds in registers per chunk
-constexpr uint32_t kRouteMaxWgs = 512;                // workgroups: rows of the (bin, workgroup) table
-constexpr int kRouteScanBlock = 1024;                 // the scan's single workgroup
 constexpr uint32_t kRouteAlign = 4;                   // DLSM_ROUTE_ALIGN: every bin's run starts at a multiple
 constexpr uint32_t kRouteStageKeyMax = 32;            // longest fixed key the 16-byte-load path stages (bytes)
 
 static_assert(kRouteWaveItems % 64 == 0, "a wave walks its share 64 Gets at a time");
-static_assert(kRouteBins <= kRouteBlock, "scatter: thread d < kRouteBins owns bin d");
-static_assert(kRouteWaveItems < (1u << (32 - kRouteBinLg)), "rank and bin share a register");
+static_assert(kRouteWaveItems < (1u << (32 - kSortBinLg)), "rank and bin share a register");
 
 // The first 16 bytes of a key, zero-padded, as two big-endian u64 (formed as
 // VersionDev::pre_small is).  If two keys' prefixes differ, their order is
@@ -68,7 +63,7 @@ struct RouteBounds {
   const RoutePrefix* pre;
   const uint64_t* off;  // n + 1
   const uint8_t* bytes;
-  uint32_t n;           // 1 .. kRouteBins - 1
+  uint32_t n;           // 1 .. kSortBins - 1
 };
 
 // Get_Target_Shard (db/db_impl_sharding.h:41-55): shards_pool.upper_bound(key)
@@ -80,7 +75,7 @@ struct RouteBounds {
 DLSM_HD uint32_t route_shard(const RouteBounds& b, const RoutePrefix& q, const uint8_t* key, uint64_t len) {
   uint32_t lo = 0;  // bounds [0, lo) have a prefix < q
 #pragma unroll
-  for (uint32_t step = kRouteBins >> 1; step; step >>= 1) {
+  for (uint32_t step = kSortBins >> 1; step; step >>= 1) {
     const uint32_t m = lo + step;
     const bool in = m <= b.n;
     const RoutePrefix p = b.pre[in ? m - 1 : 0];

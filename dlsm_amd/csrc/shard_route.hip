@@ -2,25 +2,12 @@
 // (dlsm_shard_route_dev): DBImpl_Sharding::Get_Target_Shard for every Get, and
 // each shard's Gets as one contiguous, aligned run.
 //
-// One stable counting-sort pass of the Gets by shard (the bins: the shards and
-// the "no shard" bin, at most kRouteBins, in LDS), built like a digit pass of
-// the read plan (read_plan.hip).  Three launches, ordered by the stream alone
-// (no counter is shared between workgroups, nothing inside a launch waits for
-// another workgroup):
-//   count    workgroup w walks its cpw chunks of kRouteChunk Gets, searches each
-//            Get's shard (route_shard, the bounds' prefixes in LDS), writes it
-//            as a u16 to ids[] and its count per bin to cnt[bin * nwg + w];
-//   scan     one workgroup sums every bin, rounds each bin's start up to
-//            kRouteAlign (shard_off, shard_cnt) and turns cnt into off[], the
-//            first output position of every (bin, workgroup);
-//   scatter  workgroup w reads its ids again and writes each Get's index (and
-//            its key) to off[bin * nwg + w] + (its rank among w's Gets of the
-//            bin).
-// Ranks follow item order, never the arrival order of atomics: inside a wave by
-// ballots over the bin's bits, across waves by the wave's number (each wave owns
-// a contiguous share of the chunk and a row of LDS counts), across chunks and
-// workgroups by the tables.  Gets are walked in ascending order, so each bin's
-// run comes out strictly ascending.
+// One pass of sort_pass.h over the Gets with the shard as the bin (the shards
+// and the "no shard" bin).  The count searches each Get's shard (route_shard,
+// the bounds' prefixes in LDS) and leaves it as a u16 in ids[] for the scatter;
+// the scan rounds each bin's start up to kRouteAlign (shard_off, shard_cnt);
+// the scatter writes each Get's index (and its key).  Gets are walked in
+// ascending order, so each bin's run comes out strictly ascending.
 //
 // Keys: a fixed-stride keyset whose length is a multiple of 4 (<=
 // kRouteStageKeyMax) at a 16-byte-aligned base is read 64 keys at a time with
@@ -33,7 +20,7 @@
 //
 // Bytes per Get of 20-byte keys: count 20 B in + 2 B out, scatter 2 B + 20 B in,
 // 4 B + 20 B out: 68 B with keys_out, 28 B without (the scatter then reads no
-// key).  The tables are (n_shards + 1) x nwg <= 512 x 512 entries whatever n is.
+// key).
 #include <hip/hip_runtime.h>
 
 #include "bloom_internal.h"
@@ -41,30 +28,10 @@
 namespace dlsm {
 namespace {
 
-static_assert(kRouteBlock == 64 * kRouteWaves, "wave64");
-static_assert(static_cast<uint64_t>(kRouteBins) * kRouteMaxWgs <= 0xffffffffull / 8, "table index in u32");
-static_assert(kRouteScanBlock == 1024 && kRouteBins <= kRouteScanBlock, "scan: thread d < kRouteBins owns bin d");
 static_assert(kRouteStageKeyMax % 4 == 0, "staged keys are whole dwords");
 
 constexpr uint32_t kStageUnits = 64u * kRouteStageKeyMax / 16u;  // uint4 per wave: 64 keys of the longest staged length
-constexpr uint32_t kNoItem = 0xffffffffu;
 enum : int { kKeysNone = 0, kKeysStaged = 1, kKeysBytes = 2 };
-
-__device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
-  return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
-}
-
-// The active lanes of the wave whose bin equals this lane's (bits: the bins'
-// width, the same in every lane).
-__device__ __forceinline__ uint64_t route_peers(uint32_t d, bool active, uint32_t bits) {
-  uint64_t peers = __ballot(active);
-  for (uint32_t b = 0; b < bits; b++) {
-    const bool bit = (d >> b) & 1u;
-    const uint64_t bb = __ballot(bit);
-    peers &= bit ? bb : ~bb;
-  }
-  return peers;
-}
 
 __device__ __forceinline__ uint32_t bin_bits(uint32_t bins) {  // bins >= 2
   return 32u - static_cast<uint32_t>(__builtin_clz(bins - 1u));
@@ -96,13 +63,13 @@ __device__ __forceinline__ RoutePrefix prefix_words(const uint32_t* w) {
 
 // Count: ids[g] = Get g's bin; cnt[bin * nwg + w] = workgroup w's Gets per bin.
 template <bool STAGED>
-__global__ __launch_bounds__(kRouteBlock, 8) void route_count_kernel(ShardRouteDev a) {
-  __shared__ RoutePrefix spre[kRouteBins];
-  __shared__ uint32_t hist[kRouteBins];
-  __shared__ uint4 stage[STAGED ? kRouteWaves * kStageUnits : 1];
+__global__ __launch_bounds__(kSortBlock, 8) void route_count_kernel(ShardRouteDev a) {
+  __shared__ RoutePrefix spre[kSortBins];
+  __shared__ uint32_t hist[kSortBins];
+  __shared__ uint4 stage[STAGED ? kSortWaves * kStageUnits : 1];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint32_t w = blockIdx.x;
-  for (uint32_t d = tid; d < kRouteBins; d += kRouteBlock) {
+  for (uint32_t d = tid; d < kSortBins; d += kSortBlock) {
     hist[d] = 0;
     if (d < a.bounds.n) spre[d] = a.bounds.pre[d];
   }
@@ -116,12 +83,11 @@ __global__ __launch_bounds__(kRouteBlock, 8) void route_count_kernel(ShardRouteD
   for (uint64_t c = static_cast<uint64_t>(w) * a.cpw; c < static_cast<uint64_t>(w + 1) * a.cpw; c++) {
     const uint64_t c0 = c * kRouteChunk;
     if (c0 >= n) break;
-    const uint64_t i0 = c0 + static_cast<uint64_t>(wave) * kRouteWaveItems;
-    const uint64_t i1 = i0 + kRouteWaveItems < n ? i0 + kRouteWaveItems : n;
-    for (uint64_t r = i0; r < i1; r += 64) {
+    const WaveShare sh = wave_share<kRouteChunk>(c0, wave, n);
+    for (uint64_t r = sh.i0; r < sh.i1; r += 64) {
       const uint64_t g = r + lane;
-      const bool ok = g < i1;
-      const bool whole = STAGED && r + 64 <= i1;  // the same in every lane
+      const bool ok = g < sh.i1;
+      const bool whole = STAGED && r + 64 <= sh.i1;  // the same in every lane
       uint32_t bin = 0;
       if (whole) {
         stage_keys64(kd, r, area, lane);
@@ -144,24 +110,23 @@ __global__ __launch_bounds__(kRouteBlock, 8) void route_count_kernel(ShardRouteD
         bin = route_shard(B, route_prefix(kp, l), kp, l);
       }
       if (ok) a.ids[g] = static_cast<uint16_t>(bin);  // g < n; bin <= bounds.n < bins
-      const uint64_t peers = route_peers(bin, ok, bits);
-      if (ok && lanes_below(peers) == 0) atomicAdd(&hist[bin], static_cast<uint32_t>(__builtin_popcountll(peers)));
+      hist_add(hist, bin, ok, digit_peers(__ballot(ok), bin, bits));
     }
   }
   __syncthreads();
-  for (uint32_t d = tid; d < a.bins; d += kRouteBlock) a.cnt[d * a.nwg + w] = hist[d];  // < bins * nwg
+  hist_flush(hist, a.bins, a.cnt, a.nwg, w, tid);
 }
 
 // Scan: shard_cnt[b] = the sum of bin b's counts; shard_off[b] = the previous
 // bin's end rounded up to kRouteAlign; off[b * nwg + w] = shard_off[b] + the
 // counts of b's workgroups before w.
-__global__ __launch_bounds__(kRouteScanBlock) void route_scan_kernel(ShardRouteDev a) {
-  __shared__ uint64_t tot[kRouteBins];
-  __shared__ uint64_t begin[kRouteBins];
-  __shared__ uint64_t wsum[kRouteScanBlock / 64];
+__global__ __launch_bounds__(kSortScanBlock) void route_scan_kernel(ShardRouteDev a) {
+  __shared__ uint64_t tot[kSortBins];
+  __shared__ uint64_t begin[kSortBins];
+  __shared__ uint64_t wsum[kSortScanBlock / 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint32_t nwg = a.nwg, bins = a.bins;
-  for (uint32_t b = wave; b < bins; b += kRouteScanBlock / 64) {
+  for (uint32_t b = wave; b < bins; b += kSortScanBlock / 64) {
     uint64_t s = 0;
     for (uint32_t j = lane; j < nwg; j += 64) s += a.cnt[b * nwg + j];
     for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
@@ -188,7 +153,7 @@ __global__ __launch_bounds__(kRouteScanBlock) void route_scan_kernel(ShardRouteD
     a.shard_cnt[tid] = t;
   }
   __syncthreads();
-  for (uint32_t b = wave; b < bins; b += kRouteScanBlock / 64) {
+  for (uint32_t b = wave; b < bins; b += kSortScanBlock / 64) {
     uint64_t carry = begin[b];
     for (uint32_t j0 = 0; j0 < nwg; j0 += 64) {
       const uint32_t j = j0 + lane;
@@ -204,18 +169,14 @@ __global__ __launch_bounds__(kRouteScanBlock) void route_scan_kernel(ShardRouteD
   }
 }
 
-// Scatter: every Get to off[bin * nwg + w] + its rank among workgroup w's Gets
-// of the bin.  Per chunk: (A) each wave ranks its share per bin in its own LDS
-// row, holding (bin, rank inside the share) in registers, (B) thread d turns
-// bin d's wave counts into the waves' start positions inside the chunk (the
-// chunk's own start after the chunks before is kept in its register), (C) each
-// wave places its Gets (and their keys).
+// Scatter (sort_pass.h, (A) to (C)): a wave holds its share of a chunk, and (C)
+// places the Gets and their keys.
 template <int KEYS>
-__global__ __launch_bounds__(kRouteBlock, 8) void route_scatter_kernel(ShardRouteDev a) {
-  __shared__ uint32_t tab[kRouteWaves][kRouteBins];  // (A) a wave's Gets per bin, (C) its first position in the chunk's bin
-  __shared__ uint64_t start[kRouteBins];             // the chunk's first position per bin
-  __shared__ uint4 stage[KEYS == kKeysStaged ? kRouteWaves * kStageUnits : 1];
-  static_assert(sizeof(tab) + sizeof(start) + sizeof(uint4) * kRouteWaves * kStageUnits <= 80 * 1024,
+__global__ __launch_bounds__(kSortBlock, 8) void route_scatter_kernel(ShardRouteDev a) {
+  __shared__ uint32_t tab[kSortWaves][kSortBins];  // (A) a wave's Gets per bin, (C) its first position in the chunk's bin
+  __shared__ uint64_t start[kSortBins];            // the chunk's first position per bin
+  __shared__ uint4 stage[KEYS == kKeysStaged ? kSortWaves * kStageUnits : 1];
+  static_assert(sizeof(tab) + sizeof(start) + sizeof(uint4) * kSortWaves * kStageUnits <= 80 * 1024,
                 "scatter LDS: two workgroups per CU");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint32_t w = blockIdx.x;
@@ -229,31 +190,25 @@ __global__ __launch_bounds__(kRouteBlock, 8) void route_scatter_kernel(ShardRout
   for (uint64_t c = static_cast<uint64_t>(w) * a.cpw; c < static_cast<uint64_t>(w + 1) * a.cpw; c++) {
     const uint64_t c0 = c * kRouteChunk;
     if (c0 >= n) break;
-    for (uint32_t q = lane; q < kRouteBins; q += 64) tab[wave][q] = 0;  // the wave's own row
+    for (uint32_t q = lane; q < kSortBins; q += 64) tab[wave][q] = 0;  // the wave's own row
     __builtin_amdgcn_wave_barrier();
-    const uint64_t i0 = c0 + static_cast<uint64_t>(wave) * kRouteWaveItems;
+    const uint64_t i0 = wave_share<kRouteChunk>(c0, wave, n).i0;
     uint32_t held[kRouteHold];
 #pragma unroll
     for (int q = 0; q < kRouteHold; q++) {  // the share's ids, all in flight
       const uint64_t j = i0 + 64u * q + lane;
-      held[q] = j < n ? a.ids[j] : kNoItem;
+      held[q] = j < n ? a.ids[j] : kSortNoItem;
     }
 #pragma unroll
     for (int q = 0; q < kRouteHold; q++) {
-      const bool ok = held[q] != kNoItem;
+      const bool ok = held[q] != kSortNoItem;
       const uint32_t d = ok ? held[q] : 0u;
-      const uint64_t peers = route_peers(d, ok, bits);
-      const uint32_t below = lanes_below(peers);
-      const uint32_t loc = ok ? tab[wave][d] + below : 0;
-      __builtin_amdgcn_wave_barrier();
-      if (ok && below == 0) tab[wave][d] = loc + static_cast<uint32_t>(__builtin_popcountll(peers));
-      __builtin_amdgcn_wave_barrier();
-      held[q] = ok ? (d | (loc << kRouteBinLg)) : kNoItem;
+      held[q] = rank_held(tab[wave], d, ok, digit_peers(__ballot(ok), d, bits));
     }
     __syncthreads();
     if (static_cast<uint32_t>(tid) < a.bins) {  // (B)
       uint32_t run = 0;  // <= kRouteChunk
-      for (int v = 0; v < kRouteWaves; v++) {
+      for (int v = 0; v < kSortWaves; v++) {
         const uint32_t t = tab[v][tid];
         tab[v][tid] = run;
         run += t;
@@ -269,9 +224,8 @@ __global__ __launch_bounds__(kRouteBlock, 8) void route_scatter_kernel(ShardRout
       const uint64_t j = r + lane;
       const bool whole = KEYS == kKeysStaged && r + 64 <= n;
       if (whole) stage_keys64(kd, r, area, lane);
-      if (held[q] == kNoItem) continue;
-      const uint32_t d = held[q] & (kRouteBins - 1u);
-      const uint64_t pos = start[d] + tab[wave][d] + (held[q] >> kRouteBinLg);
+      if (held[q] == kSortNoItem) continue;
+      const uint64_t pos = held_pos(held[q], tab[wave], start);
       if (pos >= a.cap) continue;  // (never: cap >= dlsm_shard_route_cap)
       a.gets[pos] = static_cast<uint32_t>(j);
       if (KEYS == kKeysStaged) {
@@ -295,15 +249,15 @@ __global__ __launch_bounds__(kRouteBlock, 8) void route_scatter_kernel(ShardRout
 }  // namespace
 
 hipError_t launch_shard_route(const ShardRouteDev& a, hipStream_t s) {
-  if (a.nwg == 0 || a.nwg > kRouteMaxWgs || a.cpw == 0 || a.bins < 2 || a.bins > kRouteBins ||
+  if (a.nwg == 0 || a.nwg > kSortMaxWgs || a.cpw == 0 || a.bins < 2 || a.bins > kSortBins ||
       a.bounds.n + 1 != a.bins)
     return hipErrorInvalidValue;
-  const dim3 grid(a.nwg), block(kRouteBlock);
+  const dim3 grid(a.nwg), block(kSortBlock);
   const bool staged = a.keys.offsets == nullptr && a.keys.key_len >= 4 && a.keys.key_len <= kRouteStageKeyMax &&
                       a.keys.key_len % 4 == 0 && (reinterpret_cast<uintptr_t>(a.keys.bytes) & 15u) == 0;
   if (staged) hipLaunchKernelGGL((route_count_kernel<true>), grid, block, 0, s, a);
   else hipLaunchKernelGGL((route_count_kernel<false>), grid, block, 0, s, a);
-  hipLaunchKernelGGL(route_scan_kernel, dim3(1), dim3(kRouteScanBlock), 0, s, a);
+  hipLaunchKernelGGL(route_scan_kernel, dim3(1), dim3(kSortScanBlock), 0, s, a);
   if (!a.keys_out) hipLaunchKernelGGL((route_scatter_kernel<kKeysNone>), grid, block, 0, s, a);
   else if (staged && (reinterpret_cast<uintptr_t>(a.keys_out) & 3u) == 0)
     hipLaunchKernelGGL((route_scatter_kernel<kKeysStaged>), grid, block, 0, s, a);

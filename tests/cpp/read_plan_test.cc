@@ -1,27 +1,15 @@
 // tests/cpp/read_plan_test.cc -- the read plan on the CPU: the task decoder
 // (dlsm_amd/csrc/read_plan.h) against brute force, the planner
-// (dlsm::plan::plan_read) and a host model of the pass structure (histogram,
-// scan and scatter per digit, walked in the kernels' item order with the
-// planner's numbers) against a stable sort.
+// (dlsm::plan::plan_read) and the host model of a pass (sort_model.h) per
+// digit, fed in the kernels' item order with the planner's numbers, against a
+// stable sort.
 // Prints "OK" on success; exits non-zero with a message otherwise.
-#include <cstdio>
-#include <cstdlib>
 #include <random>
 
-#include "../../dlsm_amd/csrc/host_plan.h"
+#include "sort_model.h"
 
 using namespace dlsm;
 using namespace dlsm::plan;
-
-#define CHECK(cond, ...)                                  \
-  do {                                                    \
-    if (!(cond)) {                                        \
-      printf("FAIL %s:%d: %s: ", __FILE__, __LINE__, #cond); \
-      printf(__VA_ARGS__);                                \
-      printf("\n");                                       \
-      exit(1);                                            \
-    }                                                     \
-  } while (0)
 
 // A version as explicit lists: level-0 files in search order, then each level's
 // files; ids are positions in search order.
@@ -85,7 +73,7 @@ static void test_decoder() {
 }
 
 static void test_planner() {
-  const uint64_t nfs[] = {0, 1, kPlanBins - 1, kPlanBins, kPlanBins + 1, 70001, 1ull << 24};
+  const uint64_t nfs[] = {0, 1, kSortBins - 1, kSortBins, kSortBins + 1, 70001, 1ull << 24};
   const uint64_t ns[] = {0, 1, 0xffffffffull};
   std::mt19937_64 rng(5);
   for (uint64_t nf : nfs)
@@ -95,7 +83,7 @@ static void test_planner() {
           ReadPlan R;
           CHECK(plan_read(n, nf, tpg, mode, R) == DLSM_OK, "plan_read");
           CHECK(R.passes >= 1 && R.passes <= kPlanMaxPasses, "passes");
-          CHECK((nf <= kPlanBins) == (R.passes == 1), "one pass iff the files fit the bins (%llu)",
+          CHECK((nf <= kSortBins) == (R.passes == 1), "one pass iff the files fit the bins (%llu)",
                 (unsigned long long)nf);
           // the digits cover the file ids: they put every id back together
           std::vector<uint64_t> ids = {0, nf ? nf - 1 : 0, nf / 2};
@@ -103,7 +91,7 @@ static void test_planner() {
           for (uint64_t f : ids) {
             uint64_t back = 0;
             for (int p = 0; p < R.passes; p++) {
-              CHECK(R.pass[p].shift == static_cast<uint32_t>(p) * kPlanDigitLg, "shift");
+              CHECK(R.pass[p].shift == static_cast<uint32_t>(p) * kSortBinLg, "shift");
               back |= static_cast<uint64_t>(plan_digit(static_cast<uint32_t>(f), R.pass[p].shift)) << R.pass[p].shift;
             }
             CHECK(back == f, "digits of %llu", (unsigned long long)f);
@@ -113,7 +101,7 @@ static void test_planner() {
           for (int p = 0; p < R.passes; p++) {
             const ReadPlanPass& P = R.pass[p];
             CHECK(P.items_max == (p == 0 ? n : R.tasks_max), "items");
-            CHECK(P.nwg <= kPlanMaxWgs && P.nwg <= R.table_wgs && P.cpw >= 1, "grid");
+            CHECK(P.nwg <= kSortMaxWgs && P.nwg <= R.table_wgs && P.cpw >= 1, "grid");
             CHECK(static_cast<unsigned __int128>(P.nwg) * P.cpw * kPlanChunk >= P.items_max, "cover");
             if (P.nwg)
               CHECK(static_cast<unsigned __int128>(P.nwg - 1) * P.cpw * kPlanChunk < P.items_max, "empty workgroup");
@@ -121,13 +109,13 @@ static void test_planner() {
             // a (workgroup, bin) count fits its u32: the Gets of a workgroup times the tasks of a Get
             CHECK(static_cast<unsigned __int128>(P.cpw) * kPlanChunk * (p == 0 ? tpg : 1) < (1ull << 32), "count");
             if (P.nwg) {
-              const uint64_t hi = static_cast<uint64_t>(kPlanBins - 1) * P.nwg + (P.nwg - 1);
+              const uint64_t hi = static_cast<uint64_t>(kSortBins - 1) * P.nwg + (P.nwg - 1);
               CHECK(hi < R.table_entries, "table index");
               CHECK(hi * sizeof(uint32_t) < R.cnt_bytes && hi * sizeof(uint64_t) < R.off_bytes, "table extent");
               CHECK((P.nwg - 1) * sizeof(uint64_t) < R.drop_bytes, "drop extent");
             }
           }
-          CHECK(R.table_entries == static_cast<uint64_t>(kPlanBins) * R.table_wgs && R.table_entries % 4 == 0, "table");
+          CHECK(R.table_entries == static_cast<uint64_t>(kSortBins) * R.table_wgs && R.table_entries % 4 == 0, "table");
           // workspace regions: aligned, inside, disjoint
           std::vector<std::pair<uint64_t, uint64_t>> ext = {
               {R.cnt_off, R.cnt_bytes},         {R.off_off, R.off_bytes},         {R.drop_off, R.drop_bytes},
@@ -202,55 +190,25 @@ static Model run_model(const Lists& L, const std::vector<uint32_t>& order, const
   ReadPlan R;
   CHECK(plan_read(n, L.n_files, plan_tasks_per_get(L.shape), mode, R) == DLSM_OK, "plan");
   Model M;
-  std::vector<Item> cur, next;
-  std::vector<uint32_t> cnt(R.table_entries);
-  std::vector<uint64_t> off(R.table_entries);
+  std::vector<Item> cur;
   uint64_t total = 0;
   for (int p = 0; p < R.passes; p++) {
     const ReadPlanPass& P = R.pass[p];
-    const uint64_t items = p == 0 ? n : total;
     // every workgroup's items, in walk order
     std::vector<std::vector<Item>> of_wg(P.nwg);
-    for (uint32_t w = 0; w < P.nwg; w++)
-      for (uint64_t c = static_cast<uint64_t>(w) * P.cpw; c < static_cast<uint64_t>(w + 1) * P.cpw; c++) {
-        const uint64_t c0 = c * kPlanChunk;
-        if (c0 >= items) break;
-        for (int wave = 0; wave < kPlanWaves; wave++) {
-          const uint64_t i0 = c0 + static_cast<uint64_t>(wave) * kPlanWaveItems;
-          const uint64_t i1 = std::min(i0 + kPlanWaveItems, items);
-          if (p == 0) {
-            uint64_t d = 0;
-            walk_masks_model(L, order, mask, pick, mode == DLSM_PLAN_ALL, i0, i1, of_wg[w], d);
-            M.dropped += d;
-          } else {
-            for (uint64_t j = i0; j < i1; j++) of_wg[w].push_back(cur[j]);
-          }
-        }
-      }
-    std::fill(cnt.begin(), cnt.end(), 0u);
-    for (uint32_t w = 0; w < P.nwg; w++)
-      for (const Item& it : of_wg[w]) {
-        const uint64_t e = static_cast<uint64_t>(plan_digit(it.key, P.shift)) * P.nwg + w;
-        CHECK(e < R.table_entries, "table index");
-        cnt[e]++;
-      }
-    uint64_t run = 0;
-    const uint64_t entries = static_cast<uint64_t>(kPlanBins) * P.nwg;
-    for (uint64_t e = 0; e < entries; e++) {
-      off[e] = run;
-      run += cnt[e];
-    }
-    total = run;
+    sort_model::walk(P.nwg, P.cpw, kPlanChunk, p == 0 ? n : total, [&](uint32_t w, uint64_t i0, uint64_t i1) {
+      if (p == 0) walk_masks_model(L, order, mask, pick, mode == DLSM_PLAN_ALL, i0, i1, of_wg[w], M.dropped);
+      else of_wg[w].insert(of_wg[w].end(), cur.begin() + i0, cur.begin() + i1);
+    });
+    sort_model::Pass<Item> S = sort_model::run_pass(of_wg, kSortBins, R.table_entries, 1, 0, Item{0, 0},
+                                                    [&](const Item& it) { return plan_digit(it.key, P.shift); });
+    total = S.end;
     CHECK(total <= R.tasks_max, "tasks bound");
     if (R.passes == 1) {
-      M.file_begin.assign(L.n_files + 1, 0);
-      for (uint32_t f = 0; f < L.n_files; f++) M.file_begin[f] = off[static_cast<uint64_t>(f) * P.nwg];
-      M.file_begin[L.n_files] = total;
+      M.file_begin.assign(S.begin.begin(), S.begin.begin() + L.n_files);
+      M.file_begin.push_back(total);
     }
-    next.assign(total, Item{0, 0});
-    for (uint32_t w = 0; w < P.nwg; w++)
-      for (const Item& it : of_wg[w]) next[off[static_cast<uint64_t>(plan_digit(it.key, P.shift)) * P.nwg + w]++] = it;
-    cur.swap(next);
+    cur.swap(S.out);
   }
   if (R.passes > 1) {
     M.file_begin.assign(L.n_files + 1, 0);
@@ -324,10 +282,11 @@ static void test_model(uint32_t n_l0, const uint32_t (&counts)[kPlanLevels], uin
 int main() {
   test_decoder();
   test_planner();
+  sort_model::test_grid();
   const uint64_t C = kPlanChunk;
   test_model(4, {8, 16, 0, 2, 1}, 3 * C + 3, false, 1);                   // one pass
-  test_model(4, {kPlanBins - 4 - 5, 1, 1, 1, 1}, C + 1, false, 2);        // bins - 1 files
-  test_model(4, {kPlanBins - 4 - 3, 1, 1, 1, 1}, 3 * C + 3, false, 3);    // bins + 1: two passes
+  test_model(4, {kSortBins - 4 - 5, 1, 1, 1, 1}, C + 1, false, 2);        // bins - 1 files
+  test_model(4, {kSortBins - 4 - 3, 1, 1, 1, 1}, 3 * C + 3, false, 3);    // bins + 1: two passes
   test_model(59, {1, 1, 1, 1, 1}, 257, false, 4);                         // 64 slots
   test_model(1, {70000, 0, 0, 0, 0}, C + 65, false, 5);                   // 70,001 files
   test_model(3, {600, 0, 5, 0, 1}, 2 * C + 7, true, 6);                   // malformed masks and picks: dropped

@@ -1,33 +1,21 @@
 // tests/cpp/shard_route_test.cc -- the shard route on the CPU: the shard search
 // the kernels run (dlsm_amd/csrc/shard_route.h) against
 // std::map<std::string, int>::upper_bound on adversarial bounds, the planner
-// (dlsm::plan::plan_shard_route, shard_route_cap, shard_route_offsets), a host
-// model of the pass structure (count, scan and scatter walked in the kernels'
-// item order with the planner's numbers) against a stable sort, and the map's
-// argument checks (plan_shardmap).
+// (dlsm::plan::plan_shard_route, shard_route_cap, shard_route_offsets), the host
+// model of the pass (sort_model.h) fed in the kernels' item order with the
+// planner's numbers against a stable sort, and the map's argument checks
+// (plan_shardmap).
 // Prints "OK" on success; exits non-zero with a message otherwise.
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
 #include <map>
 #include <random>
 #include <set>
 #include <string>
 
-#include "../../dlsm_amd/csrc/host_plan.h"
+#include "sort_model.h"
 
 using namespace dlsm;
 using namespace dlsm::plan;
-
-#define CHECK(cond, ...)                                  \
-  do {                                                    \
-    if (!(cond)) {                                        \
-      printf("FAIL %s:%d: %s: ", __FILE__, __LINE__, #cond); \
-      printf(__VA_ARGS__);                                \
-      printf("\n");                                       \
-      exit(1);                                            \
-    }                                                     \
-  } while (0)
 
 typedef std::vector<std::string> Strs;
 
@@ -133,31 +121,18 @@ static void test_search() {
 // numbers: returns gets / off / cnt.
 static void model(const std::vector<uint16_t>& bin, const ShardRoute& R, std::vector<uint64_t>& off,
                   std::vector<uint64_t>& cnt, std::vector<uint32_t>& gets, uint64_t cap) {
-  const uint64_t n = bin.size();
-  std::vector<uint64_t> table(R.table_entries, 0);
-  for (uint32_t w = 0; w < R.nwg; w++)
-    for (uint64_t c = uint64_t(w) * R.cpw; c < uint64_t(w + 1) * R.cpw; c++)
-      for (uint64_t g = c * kRouteChunk; g < std::min<uint64_t>(n, (c + 1) * kRouteChunk); g++)
-        table[uint64_t(bin[g]) * R.nwg + w]++;
-  cnt.assign(R.bins, 0);
-  for (uint32_t b = 0; b < R.bins; b++)
-    for (uint32_t w = 0; w < R.nwg; w++) cnt[b] += table[uint64_t(b) * R.nwg + w];
+  std::vector<std::vector<uint32_t>> of_wg(R.nwg);
+  sort_model::walk(R.nwg, R.cpw, kRouteChunk, bin.size(), [&](uint32_t w, uint64_t i0, uint64_t i1) {
+    for (uint64_t g = i0; g < i1; g++) of_wg[w].push_back(static_cast<uint32_t>(g));
+  });
+  sort_model::Pass<uint32_t> S = sort_model::run_pass(of_wg, R.bins, R.table_entries, kRouteAlign, cap, 0xffffffffu,
+                                                      [&](uint32_t g) { return bin[g]; });
+  cnt = S.count;
   off.assign(R.bins, 0);
   const uint64_t end = shard_route_offsets(cnt.data(), R.bins, off.data());
   CHECK(end <= cap, "end %llu cap %llu", (unsigned long long)end, (unsigned long long)cap);
-  std::vector<uint64_t> first(R.table_entries, 0);
-  for (uint32_t b = 0; b < R.bins; b++) {
-    uint64_t at = off[b];
-    for (uint32_t w = 0; w < R.nwg; w++) {
-      first[uint64_t(b) * R.nwg + w] = at;
-      at += table[uint64_t(b) * R.nwg + w];
-    }
-  }
-  gets.assign(cap, 0xffffffffu);
-  for (uint32_t w = 0; w < R.nwg; w++)
-    for (uint64_t c = uint64_t(w) * R.cpw; c < uint64_t(w + 1) * R.cpw; c++)
-      for (uint64_t g = c * kRouteChunk; g < std::min<uint64_t>(n, (c + 1) * kRouteChunk); g++)
-        gets[first[uint64_t(bin[g]) * R.nwg + w]++] = static_cast<uint32_t>(g);
+  CHECK(off == S.begin && end == S.end, "the planner's offsets are the pass's");
+  gets.swap(S.out);
 }
 
 static void test_planner() {
@@ -166,7 +141,7 @@ static void test_planner() {
   const uint64_t sizes[] = {0, 1, C - 1, C, C + 1, 3 * C + 3, uint64_t(small_cap) * C * 3 + 5};
   for (int n_shards : {1, 2, 16, 511}) {
     for (uint64_t n : sizes) {
-      for (uint32_t max_wgs : {small_cap, kRouteMaxWgs}) {
+      for (uint32_t max_wgs : {small_cap, kSortMaxWgs}) {
         ShardRoute R;
         CHECK(plan_shard_route(n, n_shards, max_wgs, R) == DLSM_OK, "n %llu", (unsigned long long)n);
         CHECK(R.bins == static_cast<uint32_t>(n_shards) + 1, "bins");
@@ -219,10 +194,10 @@ static void test_planner() {
           (unsigned long long)end);
   }
   ShardRoute R;
-  CHECK(plan_shard_route(1ull << 32, 4, kRouteMaxWgs, R) == DLSM_E_ARG, "n > UINT32_MAX");
-  CHECK(plan_shard_route(0xffffffffull, 511, kRouteMaxWgs, R) == DLSM_OK && R.nwg <= kRouteMaxWgs, "largest n");
-  CHECK(plan_shard_route(10, 0, kRouteMaxWgs, R) == DLSM_E_ARG, "no shard");
-  CHECK(plan_shard_route(10, 512, kRouteMaxWgs, R) == DLSM_E_ARG, "512 shards");
+  CHECK(plan_shard_route(1ull << 32, 4, kSortMaxWgs, R) == DLSM_E_ARG, "n > UINT32_MAX");
+  CHECK(plan_shard_route(0xffffffffull, 511, kSortMaxWgs, R) == DLSM_OK && R.nwg <= kSortMaxWgs, "largest n");
+  CHECK(plan_shard_route(10, 0, kSortMaxWgs, R) == DLSM_E_ARG, "no shard");
+  CHECK(plan_shard_route(10, 512, kSortMaxWgs, R) == DLSM_E_ARG, "512 shards");
 }
 
 static void test_map_args() {
@@ -279,6 +254,7 @@ static void test_map_args() {
 int main() {
   test_search();
   test_planner();
+  sort_model::test_grid();
   test_map_args();
   printf("OK\n");
   return 0;
