@@ -21,8 +21,8 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib as _L
-from ._lib import (BLOCK_CHECKSUM, BLOCK_FILTER, BLOCK_OK, BLOCK_SHORT, BLOCK_TYPE, BlockError, DlsmError,
-                   check, dlsm_build_job, dlsm_keyset)
+from ._lib import (BLOCK_CHECKSUM, BLOCK_FILTER, BLOCK_INDEX, BLOCK_OK, BLOCK_SHORT, BLOCK_TYPE, BlockError,
+                   DlsmError, check, dlsm_build_job, dlsm_keyset)
 
 __all__ = [
     "Keys", "Context", "FilterSet", "DlsmError", "BlockError", "BLOCK_OK", "BLOCK_SHORT", "BLOCK_CHECKSUM",
@@ -31,6 +31,8 @@ __all__ = [
     "FullFilterBlockReader", "BloomFilterPolicy", "PATH_AUTO", "PATH_DIRECT", "PATH_SLICED",
     "crc32c", "crc32c_mask", "Version", "VersionFile", "PLAN_FIRST", "PLAN_ALL", "read_plan_chunk",
     "ShardMap", "MAX_SHARDS", "ROUTE_ALIGN", "shard_route_cap", "shard_route_chunk",
+    "TableIndex", "BLOCK_INDEX", "GET_NOTFOUND", "GET_FOUND", "GET_DELETED", "GET_CORRUPT", "KV_HANDLE",
+    "index_fence_interval", "index_seek_block", "index_block_check", "index_block_seek",
 ]
 
 PATH_AUTO, PATH_DIRECT, PATH_SLICED = 0, 1, 2
@@ -43,6 +45,9 @@ OPT_VERSION_SLICE_BYTES, OPT_VERSION_PASS_SLICES = 8, 9  # sliced version probe:
 OPT_PROBE_MULTI = 10  # multi-group filter sets: 1 one pass over every group (default), 0 a pass per group
 PLAN_FIRST, PLAN_ALL = 0, 1  # dlsm_version_read_plan_dev modes: each Get's lowest set slot / every set slot
 MAX_SHARDS, ROUTE_ALIGN = 511, 4  # DLSM_MAX_SHARDS, DLSM_ROUTE_ALIGN
+GET_NOTFOUND, GET_FOUND, GET_DELETED, GET_CORRUPT = 0, 1, 2, 3  # DLSM_GET_*: a seek task's (or a Get's) state
+# dlsm_kv_handle as a numpy record (16 bytes); device arrays of it are uint8[n, 16] or int64[n, 2] tensors
+KV_HANDLE = np.dtype([("offset", "<u8"), ("size", "<u4"), ("file", "<u4")])
 
 
 def lib():
@@ -66,6 +71,39 @@ def read_plan_chunk() -> int:
 def shard_route_chunk() -> int:
     """Gets per workgroup-chunk of the shard route's kernels."""
     return int(lib().dlsm_shard_route_chunk())
+
+
+def index_fence_interval() -> int:
+    """Entries per fence of an opened table index."""
+    return int(lib().dlsm_index_fence_interval())
+
+
+def index_seek_block() -> int:
+    """Tasks per workgroup step of the index seek's kernel."""
+    return int(lib().dlsm_index_seek_block())
+
+
+def index_block_check(contents: bytes) -> Optional[int]:
+    """The open's validation of one index block's contents on the host: the
+    entry count, or None where a rule fails."""
+    a = np.frombuffer(bytes(contents) + b"\0", dtype=np.uint8)
+    n = C.c_uint64()
+    st = lib().dlsm_index_block_check(a.ctypes.data, len(contents), C.byref(n))
+    if st == _L.DLSM_E_CORRUPT:
+        return None
+    check(st, "index_block_check")
+    return int(n.value)
+
+
+def index_block_seek(contents: bytes, user_key: bytes, snapshot: int, file: int = 0):
+    """Table::InternalGet's index step for one key on the host: (state,
+    offset, size, file)."""
+    a = np.frombuffer(bytes(contents) + b"\0", dtype=np.uint8)
+    k = np.frombuffer(bytes(user_key) + b"\0", dtype=np.uint8)
+    st, h = C.c_uint8(), _L.dlsm_kv_handle()
+    check(lib().dlsm_index_block_seek(a.ctypes.data, len(contents), k.ctypes.data, len(user_key), snapshot, file,
+                                      C.byref(st), C.byref(h)), "index_block_seek")
+    return int(st.value), int(h.offset), int(h.size), int(h.file)
 
 
 def shard_route_cap(n: int, n_shards: int) -> int:
@@ -320,6 +358,49 @@ class ShardMap:
     def close(self):
         if getattr(self, "h", None):
             lib().dlsm_shardmap_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+class TableIndex:
+    """The index blocks of a version's tables resident on one device
+    (dlsm_tableindex): ``blocks[f]`` is file f's sealed index block (bytes, or
+    a device uint8 tensor with on_device) or None for a file whose index is
+    not held.  A block that fails its checks raises BlockError with every
+    file's BLOCK_* code."""
+
+    def __init__(self, ctx: "Context", blocks, on_device: bool = False, *, verify_checksums: bool = True):
+        n = len(blocks)
+        if on_device:
+            keep = list(blocks)
+            ptrs = [None if b is None else _ptr(b) for b in keep]
+            lens = [0 if b is None else int(b.numel()) for b in keep]
+        else:
+            keep = [None if b is None else np.frombuffer(bytes(b) + b"\0", dtype=np.uint8) for b in blocks]
+            ptrs = [None if a is None else a.ctypes.data for a in keep]
+            lens = [0 if a is None else a.size - 1 for a in keep]
+        pa = (C.c_void_p * max(n, 1))(*ptrs)
+        la = (C.c_uint64 * max(n, 1))(*lens)
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+        h = C.c_void_p()
+        st = lib().dlsm_tableindex_create_blocks(ctx.h, pa, la, n, 1 if on_device else 0,
+                                                 1 if verify_checksums else 0, status.ctypes.data, C.byref(h))
+        self.h = h if st == _L.DLSM_OK else None
+        if st == _L.DLSM_E_CORRUPT:
+            assert h.value is None
+            raise BlockError(st, "tableindex_create_blocks", status[:n])
+        check(st, "tableindex_create_blocks")
+        self.n_files = n
+        self.block_status = status[:n]
+        nf, ne, nb = C.c_int(), C.c_uint64(), C.c_uint64()
+        check(lib().dlsm_tableindex_size(h, C.byref(nf), C.byref(ne), C.byref(nb)), "tableindex_size")
+        self.n_entries, self.device_bytes = int(ne.value), int(nb.value)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().dlsm_tableindex_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -724,6 +805,33 @@ class Context:
         ks = keys.c()
         check(lib().dlsm_shard_route_dev(self.h, m.h, C.byref(ks), _ptr(shard_off), _ptr(shard_cnt), _ptr(gets),
                                          _ptr(keys_out), cap), "shard_route_dev")
+
+    # -- table index: the index step of Table::InternalGet ----------------------
+    def tableindex(self, blocks, on_device: bool = False, *, verify_checksums: bool = True) -> TableIndex:
+        return TableIndex(self, blocks, on_device, verify_checksums=verify_checksums)
+
+    def index_seek_dev(self, ti: TableIndex, keys: Keys, snapshot: int, file_begin, gets, *, cap: Optional[int] = None,
+                       task_state=None, task_handle=None, get_state=None, get_handle=None):
+        """Seek every task of a read plan (file_begin, gets: the plan's device
+        outputs) in its file's index block.  task_state (device uint8[cap]) /
+        task_handle (device, 16 bytes per task: KV_HANDLE) are written per
+        task; get_state (device uint8[n]) / get_handle (16 bytes per Get) only
+        where a task's state is not GET_NOTFOUND -- zero-fill them before the
+        first round of a PLAN_FIRST loop; get_state is then the ``hit`` of
+        version_masks_advance_dev.  Asynchronous; cap defaults to gets' length."""
+        cap = (0 if gets is None else int(gets.numel())) if cap is None else int(cap)
+        _need(file_begin, 8 * (ti.n_files + 1), "file_begin")
+        _need(gets, 4 * cap, "gets")
+        for x, per, what in ((task_state, 1, "task_state"), (task_handle, 16, "task_handle")):
+            if x is not None:
+                _need(x, per * cap, what)
+        for x, per, what in ((get_state, 1, "get_state"), (get_handle, 16, "get_handle")):
+            if x is not None:
+                _need(x, per * keys.n, what)
+        ks = keys.c()
+        check(lib().dlsm_index_seek_dev(self.h, ti.h, C.byref(ks), snapshot, _ptr(file_begin), _ptr(gets), cap,
+                                        _ptr(task_state), _ptr(task_handle), _ptr(get_state), _ptr(get_handle)),
+              "index_seek_dev")
 
     # -- full filter probe --------------------------------------------------
     def filterset(self, filters, on_device: bool = False, *, sealed: bool = False,

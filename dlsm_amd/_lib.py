@@ -49,6 +49,10 @@ class dlsm_version_file(C.Structure):
                 ("filter", C.c_void_p), ("filter_len", C.c_uint64)]
 
 
+class dlsm_kv_handle(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("size", C.c_uint32), ("file", C.c_uint32)]
+
+
 class DlsmError(RuntimeError):
     def __init__(self, status: int, what: str = ""):
         self.status = status
@@ -56,7 +60,7 @@ class DlsmError(RuntimeError):
         super().__init__(f"{what}: {msg} ({status})" if what else f"{msg} ({status})")
 
 
-BLOCK_OK, BLOCK_SHORT, BLOCK_CHECKSUM, BLOCK_TYPE, BLOCK_FILTER = 0, 1, 2, 3, 4  # DLSM_BLOCK_*
+BLOCK_OK, BLOCK_SHORT, BLOCK_CHECKSUM, BLOCK_TYPE, BLOCK_FILTER, BLOCK_INDEX = 0, 1, 2, 3, 4, 5  # DLSM_BLOCK_*
 
 
 class BlockError(DlsmError):
@@ -154,6 +158,19 @@ SIGNATURES = [
     ("dlsm_shard_route", C.c_int, [_VP, _VP, C.POINTER(dlsm_keyset), _VP, _VP, _VP, _VP, C.c_uint64]),
     ("dlsm_shard_route_cap", C.c_uint64, [C.c_uint64, C.c_int]),
     ("dlsm_shard_route_chunk", C.c_uint32, []),
+    ("dlsm_tableindex_create_blocks", C.c_int, [_VP, C.POINTER(_VP), _U64P, C.c_int, C.c_int, C.c_int, _VP,
+                                                C.POINTER(_VP)]),
+    ("dlsm_tableindex_destroy", C.c_int, [_VP]),
+    ("dlsm_tableindex_size", C.c_int, [_VP, C.POINTER(C.c_int), _U64P, _U64P]),
+    ("dlsm_index_seek_dev", C.c_int, [_VP, _VP, C.POINTER(dlsm_keyset), C.c_uint64, _VP, _VP, C.c_uint64,
+                                      _VP, _VP, _VP, _VP]),
+    ("dlsm_index_seek", C.c_int, [_VP, _VP, C.POINTER(dlsm_keyset), C.c_uint64, _VP, _VP, C.c_uint64,
+                                  _VP, _VP, _VP, _VP]),
+    ("dlsm_index_block_check", C.c_int, [_VP, C.c_uint64, _U64P]),
+    ("dlsm_index_block_seek", C.c_int, [_VP, C.c_uint64, _VP, C.c_uint64, C.c_uint64, C.c_uint32,
+                                        C.POINTER(C.c_uint8), C.POINTER(dlsm_kv_handle)]),
+    ("dlsm_index_fence_interval", C.c_uint32, []),
+    ("dlsm_index_seek_block", C.c_uint32, []),
     ("dlsm_bloom_full_probe", C.c_int, [_VP, _VP, C.POINTER(dlsm_keyset), _VP]),
     ("dlsm_bloom_full_probe_hashed_dev", C.c_int, [_VP, _VP, C.POINTER(dlsm_keyset), _VP]),
     ("dlsm_bloom_hash_batch", C.c_int, [C.POINTER(dlsm_keyset), _VP, C.c_int]),

@@ -1447,8 +1447,20 @@ namespace {
 // Verify (and copy, where dst differs from src) the device-resident blocks
 // `blk`; recs gets one record per block.  One upload of the work list, two
 // launches, one D2H, one synchronisation.
+int queue_ingest(dlsm_ctx* ctx, const std::vector<IngestBlock>& blk, bool verify, bool parse,
+                 std::vector<IngestRecord>& recs);
 int run_ingest(dlsm_ctx* ctx, const std::vector<IngestBlock>& blk, bool verify, bool parse,
                std::vector<IngestRecord>& recs) {
+  DLSM_CHECK(queue_ingest(ctx, blk, verify, parse, recs));
+  if (!blk.empty()) DLSM_TRY(ctx_sync(ctx, ctx->stream));
+  return DLSM_OK;
+}
+
+// run_ingest without its synchronisation: the caller queues more work behind
+// the pass (ctx->ing_rec.p holds the records on the device) and syncs once;
+// recs is filled by then.
+int queue_ingest(dlsm_ctx* ctx, const std::vector<IngestBlock>& blk, bool verify, bool parse,
+                 std::vector<IngestRecord>& recs) {
   const size_t n = blk.size();
   recs.assign(n, IngestRecord{});
   if (n == 0) return DLSM_OK;
@@ -1480,7 +1492,6 @@ int run_ingest(dlsm_ctx* ctx, const std::vector<IngestBlock>& blk, bool verify, 
                                static_cast<uint32_t>(parts), verify, parse, ctx->ing_partial.p, ctx->ing_rec.p, s));
   DLSM_TRY(hipEventRecord(ctx->ev_ing1, s));
   DLSM_TRY(hipMemcpyAsync(recs.data(), ctx->ing_rec.p, sizeof(IngestRecord) * n, hipMemcpyDeviceToHost, s));
-  DLSM_TRY(ctx_sync(ctx, s));
   ctx->ing_read = rd;
   ctx->ing_written = wr;
   return DLSM_OK;
@@ -2580,6 +2591,220 @@ int dlsm_shard_route(dlsm_ctx* ctx, const dlsm_shardmap* map, const dlsm_keyset*
       DLSM_TRY(hipMemcpyAsync(keys_out + shard_off[b] * keys->key_len, st + ko + shard_off[b] * keys->key_len,
                               shard_cnt[b] * keys->key_len, hipMemcpyDeviceToHost, s));
   }
+  DLSM_TRY(ctx_sync(ctx, s));
+  return DLSM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Table index: Table::InternalGet's index step (table/table.cc:452-513) for a
+// planned Get batch (index_seek.hip)
+// ---------------------------------------------------------------------------
+static_assert(sizeof(dlsm_kv_handle) == sizeof(KvHandle) && offsetof(dlsm_kv_handle, size) == offsetof(KvHandle, size) &&
+                  offsetof(dlsm_kv_handle, file) == offsetof(KvHandle, file),
+              "handle layout");
+static_assert(DLSM_GET_NOTFOUND == kGetNotFound && DLSM_GET_FOUND == kGetFound && DLSM_GET_DELETED == kGetDeleted &&
+                  DLSM_GET_CORRUPT == kGetCorrupt,
+              "Get states");
+
+struct dlsm_tableindex {
+  int device = 0;
+  int n_files = 0;
+  uint64_t n_entries = 0;
+  uint64_t bytes = 0;
+  uint8_t* arena = nullptr;       // the held files' blocks, each at a multiple of 256 bytes
+  IndexFileDev* files = nullptr;  // n_files records
+  RoutePrefix* fence = nullptr;   // the fence table
+  uint64_t* slot0 = nullptr;      // the open's slot prefix sums
+};
+
+// The device half of the open: copy + crc (the ingest pass), the validation
+// launches and the records' way back, behind one synchronisation.
+static int tableindex_open(dlsm_ctx* ctx, const uint8_t* const* blocks, const uint64_t* lens, int blocks_are_device,
+                           bool verify, const IndexOpen& P, dlsm_tableindex* ti, std::vector<uint8_t>& st) {
+  hipStream_t s = ctx->stream;
+  const int n_files = ti->n_files;
+  DLSM_TRY(hipMalloc(reinterpret_cast<void**>(&ti->arena), std::max<uint64_t>(P.arena_bytes, 256)));
+  DLSM_TRY(hipMalloc(reinterpret_cast<void**>(&ti->files), sizeof(IndexFileDev) * std::max(n_files, 1)));
+  DLSM_TRY(hipMalloc(reinterpret_cast<void**>(&ti->fence), sizeof(RoutePrefix) * std::max<uint64_t>(P.fences, 1)));
+  DLSM_TRY(hipMalloc(reinterpret_cast<void**>(&ti->slot0), sizeof(uint64_t) * P.slot0.size()));
+  ti->bytes = P.arena_bytes + sizeof(IndexFileDev) * n_files + sizeof(RoutePrefix) * P.fences;
+  std::vector<IndexFileDev> h(n_files, IndexFileDev{});
+  std::vector<IngestBlock> blk;
+  blk.reserve(P.held);
+  for (int f = 0; f < n_files; f++) {
+    if (!blocks[f]) continue;
+    uint8_t* slot = ti->arena + P.arena_off[f];
+    h[f].data = slot;
+    h[f].fence0 = P.fence0[f];
+    h[f].len = static_cast<uint32_t>(lens[f] >= 5 ? lens[f] - 5 : 0);
+    h[f].rec = P.rec[f];
+    IngestBlock b{blocks[f], slot, lens[f]};
+    if (!blocks_are_device) {  // one copy to the slot, then the pass runs in place
+      b.src = slot;
+      if (lens[f]) DLSM_TRY(hipMemcpyAsync(slot, blocks[f], lens[f], hipMemcpyHostToDevice, s));
+    }
+    blk.push_back(b);
+  }
+  DLSM_CHECK(ctx_upload(ctx, ti->files, h.data(), sizeof(IndexFileDev) * n_files, s));
+  DLSM_CHECK(ctx_upload(ctx, ti->slot0, P.slot0.data(), sizeof(uint64_t) * P.slot0.size(), s));
+  std::vector<IngestRecord> recs;
+  DLSM_CHECK(queue_ingest(ctx, blk, verify, false, recs));
+  DLSM_TRY(launch_index_open(ti->files, ctx->ing_rec.p, ti->slot0, static_cast<uint32_t>(n_files), P.slots, ti->fence, s));
+  if (n_files) DLSM_TRY(hipMemcpyAsync(h.data(), ti->files, sizeof(IndexFileDev) * n_files, hipMemcpyDeviceToHost, s));
+  DLSM_TRY(ctx_sync(ctx, s));
+  int ret = DLSM_OK;
+  for (int f = 0; f < n_files; f++) {
+    st[f] = DLSM_BLOCK_OK;
+    if (!blocks[f]) continue;
+    const uint32_t r = recs[P.rec[f]].status;
+    st[f] = static_cast<uint8_t>(r != DLSM_INGEST_OK ? r : (h[f].bad ? DLSM_BLOCK_INDEX : DLSM_BLOCK_OK));
+    if (st[f] != DLSM_BLOCK_OK) ret = DLSM_E_CORRUPT;
+    ti->n_entries += h[f].n;
+  }
+  return ret;
+}
+
+int dlsm_tableindex_create_blocks(dlsm_ctx* ctx, const uint8_t* const* blocks, const uint64_t* lens, int n_files,
+                                  int blocks_are_device, int verify_checksums, uint8_t* status,
+                                  dlsm_tableindex** out) {
+  if (!out) return DLSM_E_ARG;
+  *out = nullptr;
+  if (!ctx || n_files < 0 || (n_files > 0 && (!blocks || !lens))) return DLSM_E_ARG;
+  std::vector<uint8_t> present(n_files);
+  for (int f = 0; f < n_files; f++) present[f] = blocks[f] != nullptr;
+  IndexOpen P;
+  DLSM_CHECK(plan_index_open(lens, present.data(), n_files, kIndexFenceS, P));
+  if (ctx->fault) return -ctx->fault;
+  DeviceGuard g(ctx->device);
+  dlsm_tableindex* ti = new (std::nothrow) dlsm_tableindex();
+  if (!ti) return DLSM_E_NOMEM;
+  ti->device = ctx->device;
+  ti->n_files = n_files;
+  std::vector<uint8_t> st(n_files, DLSM_BLOCK_OK);
+  const int ret = tableindex_open(ctx, blocks, lens, blocks_are_device, verify_checksums != 0, P, ti, st);
+  if (status && (ret == DLSM_OK || ret == DLSM_E_CORRUPT) && n_files) memcpy(status, st.data(), n_files);
+  if (ret != DLSM_OK) {
+    dlsm_tableindex_destroy(ti);
+    return ret;
+  }
+  (void)hipFree(ti->slot0);  // the open's only
+  ti->slot0 = nullptr;
+  *out = ti;
+  return DLSM_OK;
+}
+
+int dlsm_tableindex_destroy(dlsm_tableindex* ti) {
+  if (!ti) return DLSM_OK;
+  DeviceGuard g(ti->device);
+  if (ti->slot0) (void)hipFree(ti->slot0);
+  if (ti->fence) (void)hipFree(ti->fence);
+  if (ti->files) (void)hipFree(ti->files);
+  if (ti->arena) (void)hipFree(ti->arena);
+  delete ti;
+  return DLSM_OK;
+}
+
+int dlsm_tableindex_size(const dlsm_tableindex* ti, int* n_files, uint64_t* n_entries, uint64_t* device_bytes) {
+  if (!ti) return DLSM_E_ARG;
+  if (n_files) *n_files = ti->n_files;
+  if (n_entries) *n_entries = ti->n_entries;
+  if (device_bytes) *device_bytes = ti->bytes;
+  return DLSM_OK;
+}
+
+uint32_t dlsm_index_fence_interval(void) { return kIndexFenceS; }
+uint32_t dlsm_index_seek_block(void) { return kIndexSeekBlock; }
+
+int dlsm_index_block_check(const uint8_t* contents, uint64_t len, uint64_t* n_entries) {
+  if (n_entries) *n_entries = 0;
+  if (!contents && len) return DLSM_E_ARG;
+  IndexView v;
+  if (!index_header_valid(contents, len, &v)) return DLSM_E_CORRUPT;
+  for (uint32_t i = 0; i < v.n; i++)
+    if (!index_entry_valid(v, i)) return DLSM_E_CORRUPT;
+  if (n_entries) *n_entries = v.n;
+  return DLSM_OK;
+}
+
+int dlsm_index_block_seek(const uint8_t* contents, uint64_t len, const uint8_t* user_key, uint64_t key_len,
+                          uint64_t snapshot, uint32_t file, uint8_t* state, dlsm_kv_handle* handle) {
+  if (state) *state = DLSM_GET_NOTFOUND;
+  if (handle) *handle = dlsm_kv_handle{0, 0, 0};
+  if ((!contents && len) || (!user_key && key_len) || key_len > 0xffffffffull) return DLSM_E_ARG;
+  if (snapshot > ((uint64_t(1) << 56) - 1)) return DLSM_E_ARG;
+  IndexView v;
+  if (!index_view(contents, len, &v)) return DLSM_E_CORRUPT;
+  KvHandle h;
+  const uint8_t st = index_block_seek(v, user_key, static_cast<uint32_t>(key_len), snapshot, file, &h);
+  if (state) *state = st;
+  if (handle) *handle = dlsm_kv_handle{h.offset, h.size, h.file};
+  return DLSM_OK;
+}
+
+int dlsm_index_seek_dev(dlsm_ctx* ctx, const dlsm_tableindex* ti, const dlsm_keyset* keys, uint64_t snapshot,
+                        const uint64_t* file_begin_dev, const uint32_t* gets_dev, uint64_t cap,
+                        uint8_t* task_state_dev, dlsm_kv_handle* task_handle_dev, uint8_t* get_state_dev,
+                        dlsm_kv_handle* get_handle_dev) {
+  if (!ctx || !ti || !keys || ti->device != ctx->device) return DLSM_E_ARG;
+  if (snapshot > ((uint64_t(1) << 56) - 1)) return DLSM_E_ARG;  // kMaxSequenceNumber
+  DLSM_CHECK(validate_keyset(*keys));
+  if (keys->n > 0xffffffffull || !file_begin_dev || (cap > 0 && !gets_dev)) return DLSM_E_ARG;
+  if (ctx->fault) return -ctx->fault;
+  if (ti->n_files == 0 || cap == 0) return DLSM_OK;
+  DeviceGuard g(ctx->device);
+  IndexSeekDev a{};
+  a.files = ti->files;
+  a.fence = ti->fence;
+  a.n_files = static_cast<uint32_t>(ti->n_files);
+  a.keys = to_desc(*keys);
+  a.trailer = index_seek_trailer(snapshot);
+  a.file_begin = file_begin_dev;
+  a.gets = gets_dev;
+  a.cap = cap;
+  a.task_state = task_state_dev;
+  a.task_handle = reinterpret_cast<KvHandle*>(task_handle_dev);
+  a.get_state = get_state_dev;
+  a.get_handle = reinterpret_cast<KvHandle*>(get_handle_dev);
+  DLSM_TRY(launch_index_seek(a, plan_index_seek_wgs(cap, kIndexSeekMaxWgs), ctx->stream));
+  return DLSM_OK;
+}
+
+int dlsm_index_seek(dlsm_ctx* ctx, const dlsm_tableindex* ti, const dlsm_keyset* keys, uint64_t snapshot,
+                    const uint64_t* file_begin, const uint32_t* gets, uint64_t cap, uint8_t* task_state,
+                    dlsm_kv_handle* task_handle, uint8_t* get_state, dlsm_kv_handle* get_handle) {
+  if (!ctx || !ti || !keys || !file_begin || ti->device != ctx->device) return DLSM_E_ARG;
+  DLSM_CHECK(validate_keyset(*keys));
+  if (keys->n > 0xffffffffull || snapshot > ((uint64_t(1) << 56) - 1)) return DLSM_E_ARG;
+  const uint64_t nf = static_cast<uint64_t>(ti->n_files), n = keys->n;
+  const uint64_t limit = std::min(file_begin[nf], cap);
+  if (limit > 0 && !gets) return DLSM_E_ARG;
+  if (ctx->fault) return -ctx->fault;
+  if (limit == 0) return DLSM_OK;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = ctx->stream;
+  const dlsm_keyset* sets[1] = {keys};
+  std::vector<dlsm_keyset> dk;
+  DLSM_CHECK(stage_keys(ctx, sets, 1, dk));
+  // staging: [file_begin | gets | task states | task handles | get states | get handles]
+  Layout L;
+  const uint64_t fo = L.take(8 * (nf + 1)), go = L.take(4 * limit), tso = L.take(limit), tho = L.take(16 * limit),
+                 gso = L.take(n), gho = L.take(16 * n);
+  DLSM_CHECK(ctx->st_out.ensure(L.at));
+  uint8_t* st = ctx->st_out.p;
+  DLSM_TRY(hipMemcpyAsync(st + fo, file_begin, 8 * (nf + 1), hipMemcpyHostToDevice, s));
+  DLSM_TRY(hipMemcpyAsync(st + go, gets, 4 * limit, hipMemcpyHostToDevice, s));
+  // the Get arrays are written only where a task found something: what the caller holds goes in first
+  if (get_state && n) DLSM_TRY(hipMemcpyAsync(st + gso, get_state, n, hipMemcpyHostToDevice, s));
+  if (get_handle && n) DLSM_TRY(hipMemcpyAsync(st + gho, get_handle, 16 * n, hipMemcpyHostToDevice, s));
+  DLSM_CHECK(dlsm_index_seek_dev(ctx, ti, &dk[0], snapshot, reinterpret_cast<uint64_t*>(st + fo),
+                                 reinterpret_cast<uint32_t*>(st + go), limit, task_state ? st + tso : nullptr,
+                                 task_handle ? reinterpret_cast<dlsm_kv_handle*>(st + tho) : nullptr,
+                                 get_state ? st + gso : nullptr,
+                                 get_handle ? reinterpret_cast<dlsm_kv_handle*>(st + gho) : nullptr));
+  if (task_state) DLSM_TRY(hipMemcpyAsync(task_state, st + tso, limit, hipMemcpyDeviceToHost, s));
+  if (task_handle) DLSM_TRY(hipMemcpyAsync(task_handle, st + tho, 16 * limit, hipMemcpyDeviceToHost, s));
+  if (get_state && n) DLSM_TRY(hipMemcpyAsync(get_state, st + gso, n, hipMemcpyDeviceToHost, s));
+  if (get_handle && n) DLSM_TRY(hipMemcpyAsync(get_handle, st + gho, 16 * n, hipMemcpyDeviceToHost, s));
   DLSM_TRY(ctx_sync(ctx, s));
   return DLSM_OK;
 }

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "bloom_math.h"
+#include "index_seek.h"
 #include "read_plan.h"
 #include "shard_route.h"
 
@@ -455,5 +456,42 @@ struct IngestRecord {
 uint64_t ingest_block_parts(uint64_t len);
 hipError_t launch_block_ingest(const IngestBlock* blocks, const uint32_t* part0, uint32_t n, uint32_t total_parts,
                                bool verify, bool parse, uint32_t* partial, IngestRecord* rec, hipStream_t s);
+
+// index_seek.hip: the opened index blocks of a table set (dlsm_tableindex) and
+// the batched seek (dlsm_index_seek_dev).  One file as the kernels see it; the
+// host fills data, fence0, len and rec, the open's header launch the rest.
+struct IndexFileDev {
+  const uint8_t* data;  // the block's contents in the arena; nullptr: no index held
+  uint64_t fence0;      // the file's first fence in the fence table
+  uint32_t len;         // content bytes
+  uint32_t rec;         // the block's record of the ingest pass
+  uint32_t restarts;    // offset of the restart array
+  uint32_t n;           // entries
+  uint32_t bad;         // non-zero: a validation rule failed
+  uint32_t reserved;
+};
+static_assert(sizeof(IndexFileDev) == 40, "index file record layout");
+constexpr int kIndexSeekBlock = 256;               // threads = tasks per step of a seek workgroup
+constexpr uint32_t kIndexSeekMaxWgs = 2048;        // 8 workgroups on each of 256 CUs
+constexpr uint32_t kIndexSeekLdsFiles = 1023;      // file_begin sits in LDS up to this many files (8 KiB)
+struct IndexSeekDev {
+  const IndexFileDev* files;
+  const RoutePrefix* fence;
+  uint32_t n_files;
+  KeyDesc keys;
+  uint64_t trailer;            // index_seek_trailer(snapshot)
+  const uint64_t* file_begin;  // u64[n_files + 1] (the read plan's)
+  const uint32_t* gets;        // u32[cap]
+  uint64_t cap;
+  uint8_t* task_state;         // u8[cap] or nullptr
+  KvHandle* task_handle;       // [cap] or nullptr
+  uint8_t* get_state;          // u8[keys.n] or nullptr
+  KvHandle* get_handle;        // [keys.n] or nullptr
+};
+// Header and entry launches over the files' slots (slot0: n_files + 1 prefix
+// sums; plan::IndexOpen); rec: the ingest pass's records.
+hipError_t launch_index_open(IndexFileDev* files, const IngestRecord* rec, const uint64_t* slot0, uint32_t n_files,
+                             uint64_t slots, RoutePrefix* fence, hipStream_t s);
+hipError_t launch_index_seek(const IndexSeekDev& a, uint32_t nwg, hipStream_t s);
 
 }  // namespace dlsm

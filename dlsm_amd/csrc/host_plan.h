@@ -914,5 +914,51 @@ inline int plan_shardmap(const uint8_t* const* bounds, const uint64_t* lens, int
   return DLSM_OK;
 }
 
+// ---- table index (index_seek.hip) ----------------------------------------------
+// dlsm_tableindex_create_blocks from the blocks' lengths alone: each held
+// file's slot in the arena (256-byte aligned, the whole sealed block: host
+// blocks are verified in place), its entry slots (the most entries len content
+// bytes can hold) and its fences (one per S slots).  present[f] == 0: no index
+// is held for file f.
+struct IndexOpen {
+  std::vector<uint64_t> arena_off;  // per file
+  std::vector<uint64_t> fence0;     // per file
+  std::vector<uint64_t> slot0;      // n_files + 1
+  std::vector<uint32_t> rec;        // per file: its position among the held files
+  uint32_t held = 0;
+  uint64_t arena_bytes = 0, fences = 0, slots = 0;
+};
+
+inline int plan_index_open(const uint64_t* lens, const uint8_t* present, int n_files, uint32_t S, IndexOpen& P) {
+  if (n_files < 0 || S == 0 || (n_files > 0 && (!lens || !present))) return DLSM_E_ARG;
+  P = IndexOpen();
+  P.arena_off.assign(n_files, 0);
+  P.fence0.assign(n_files, 0);
+  P.rec.assign(n_files, 0);
+  P.slot0.assign(static_cast<size_t>(n_files) + 1, 0);
+  for (int f = 0; f < n_files; f++) {
+    P.slot0[f] = P.slots;
+    if (!present[f]) continue;
+    if (lens[f] > 0xffffffffull) return DLSM_E_ARG;  // Block's offsets are 32 bits
+    const uint64_t content = lens[f] >= 5 ? lens[f] - 5 : 0;
+    const uint64_t most = content >= 4 ? (content - 4) / kIndexEntryMinBytes : 0;
+    P.arena_off[f] = P.arena_bytes;
+    P.arena_bytes += (lens[f] + 255) & ~uint64_t(255);
+    P.fence0[f] = P.fences;
+    P.fences += (most + S - 1) / S;
+    P.slots += most;
+    P.rec[f] = P.held++;
+  }
+  P.slot0[n_files] = P.slots;
+  return DLSM_OK;
+}
+
+// The seek's grid: a workgroup per kIndexSeekBlock tasks of the capacity, at
+// most max_wgs; the kernel splits the true total (read on the device) evenly.
+inline uint32_t plan_index_seek_wgs(uint64_t cap, uint32_t max_wgs) {
+  const uint64_t w = (cap + kIndexSeekBlock - 1) / kIndexSeekBlock;
+  return static_cast<uint32_t>(std::min<uint64_t>(std::max<uint64_t>(w, 1), max_wgs));
+}
+
 }  // namespace plan
 }  // namespace dlsm

@@ -120,3 +120,21 @@ def dbbench_version(ctx, dev, space: int = 100_000_000, seed: int = 11):
         files.append(VersionFile(0, 900_000 + j, key(lo), key(int(vals[-1])), ((seq + 10 + j) << 8) | 1,
                                  build(vals)))
     return files
+
+
+def dbbench_version_ranges(space: int = 100_000_000, seed: int = 11):
+    """dbbench_version's files as (first value, step, count), in its order: the
+    keys each file's filter holds, for callers that write the tables' other
+    blocks (scripts/bench_index_seek.py)."""
+    out = []
+    rng = np.random.default_rng(seed)
+    for level, nf, stride in VERSION_SHAPE:
+        edges = np.linspace(0, space, nf + 1).astype(np.int64)
+        for q in range(nf):
+            lo, hi = int(edges[q]) + (level - 1), int(edges[q + 1]) - 1
+            out.append((lo, stride, len(range(lo, hi, stride))))
+    for _ in range(4):
+        lo = int(rng.integers(0, space - 153_846 * 600))
+        step = int(rng.integers(50, 600))
+        out.append((lo, step, 153_846))
+    return out

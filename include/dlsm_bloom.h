@@ -623,6 +623,109 @@ uint64_t dlsm_shard_route_cap(uint64_t n, int n_shards);
  * tests are built). */
 uint32_t dlsm_shard_route_chunk(void);
 
+/* ---- table index: the index step of Table::InternalGet ------------------ */
+
+/* dLSM's tables are byte-addressable: TableBuilder_BACS::Add writes one index
+ * entry per key-value pair -- the internal key and BlockHandle{offset, size} of
+ * that pair -- at restart interval 1 (table/table_builder_bacs.cpp:27, :195-206),
+ * and Table::InternalGet decides a Get from the index block alone
+ * (table/table.cc:452-513): iiter->Seek(k) (table/block.h:205-273), a user-key
+ * compare, and only then the read of the pair the handle names.  These calls
+ * are that step for the tasks of a read plan, so probe -> plan(FIRST) -> seek
+ * -> advance runs on the device with no host read in the loop body.  The reads
+ * of the values stay with the caller.
+ *
+ * dlsm_tableindex_create_blocks: blocks[f] (lens[f] bytes) is file f's sealed
+ * index block, [contents][type 0][masked crc32c] (table_builder_bacs.cpp:
+ * 313-358); f is the caller's index, the numbering of the files[] array of
+ * dlsm_version_create[_blocks] and of the read plan's file_begin.  blocks[f] ==
+ * NULL: no index is held for f, and every task on f answers DLSM_GET_NOTFOUND.
+ * Each block is copied and crc-checked like a filter block, then validated so
+ * that no seek can read outside it: len >= 4, num_restarts <= (len - 4) / 4
+ * (table/block.cc:18-35; 0 restarts is an empty table), restart[0] == 0 and the
+ * restart offsets strictly ascending, every entry decodable by DecodeEntry
+ * (block.h:63-83) with shared == 0 (block.h:235) and non_shared >= 8
+ * (block_builder.cc:88), ending exactly where the next entry (or the restart
+ * array) starts, its value two varint64s (table/format.cc:23-29) with a size
+ * below 2^32, and sorting strictly after its predecessor under
+ * InternalKeyComparator (db/dbformat.cc:41-57) -- the reference asserts the
+ * order in debug builds only (block_builder.cc:91-92); the binary search needs
+ * it.  status (host u8[n_files] or NULL) gets every file's DLSM_BLOCK_* code in
+ * the caller's order (NULL blocks: DLSM_BLOCK_OK); any failure sets *out = NULL
+ * and returns DLSM_E_CORRUPT.  A fixed number of launches and one
+ * synchronisation whatever n_files is. */
+typedef struct dlsm_tableindex dlsm_tableindex;
+#define DLSM_BLOCK_INDEX 5 /* contents Block's ctor or Block::Iter::Seek would reject or misread */
+
+int dlsm_tableindex_create_blocks(dlsm_ctx* ctx, const uint8_t* const* blocks, const uint64_t* lens, int n_files,
+                                  int blocks_are_device, int verify_checksums, uint8_t* status,
+                                  dlsm_tableindex** out);
+int dlsm_tableindex_destroy(dlsm_tableindex* ti);
+int dlsm_tableindex_size(const dlsm_tableindex* ti, int* n_files, uint64_t* n_entries, uint64_t* device_bytes);
+
+/* dlsm_index_seek_dev: file_begin_dev[n_files + 1] and gets_dev[cap] are the
+ * read plan's outputs; the task total is read on the device from
+ * file_begin_dev[n_files], tasks at positions >= cap are not touched.  keys is
+ * the batch the plan's Get indices refer to (user keys, or internal keys with
+ * suffix_len = 8 of which ExtractUserKey is used; fixed-stride or
+ * variable-length).  Task t = (Get g = gets[t], file f with file_begin[f] <= t <
+ * file_begin[f + 1]):
+ *   the target is LookupKey(user_key, snapshot) (db/dbformat.h:74-81);
+ *   e = the first entry of f whose internal key is >= the target (user keys
+ *       ascending bytewise, trailers descending) -- where Seek leaves the iterator;
+ *   no such entry                  DLSM_GET_NOTFOUND
+ *   e's type byte > 1              DLSM_GET_CORRUPT  (ParseInternalKey fails,
+ *                                  dbformat.h:451-461; no user-key compare follows)
+ *   e's user key differs           DLSM_GET_NOTFOUND
+ *   type 1 / type 0                DLSM_GET_FOUND / DLSM_GET_DELETED (SaveValue,
+ *                                  db/version_set.h:61-75)
+ *   every state but NOTFOUND carries e's decoded BlockHandle and f.
+ * Outputs (device, each may be NULL):
+ *   task_state_dev u8[cap], task_handle_dev [cap]: written for every task below
+ *       min(total, cap), NOTFOUND with a zero handle -- a pure function of the
+ *       inputs for any plan mode; an ALL plan (a Get in several files) uses these;
+ *   get_state_dev u8[n], get_handle_dev [n]: indexed by g, written only where
+ *       the state is not NOTFOUND; defined when no Get has two tasks (a FIRST
+ *       plan).  The caller zero-fills them once before the first round; after
+ *       each round get_state_dev is the hit_dev of dlsm_version_masks_advance_dev,
+ *       and after the last round they hold Version::Get's outcome per Get
+ *       (db/version_set.cc:415-425: every non-zero state ends the search).
+ * A gets entry >= keys->n answers NOTFOUND.  DLSM_OPT_FAULT_INJECT makes the
+ * calls return the injected error.  Asynchronous on the context's stream: no
+ * host read-back.  dlsm_index_seek is the host-memory form (every array on the
+ * host; the Get arrays are read, updated and written back).  Synchronous. */
+typedef struct {
+  uint64_t offset;
+  uint32_t size;
+  uint32_t file;
+} dlsm_kv_handle; /* 16 bytes */
+#define DLSM_GET_NOTFOUND 0
+#define DLSM_GET_FOUND 1
+#define DLSM_GET_DELETED 2
+#define DLSM_GET_CORRUPT 3
+
+int dlsm_index_seek_dev(dlsm_ctx* ctx, const dlsm_tableindex* ti, const dlsm_keyset* keys, uint64_t snapshot,
+                        const uint64_t* file_begin_dev, const uint32_t* gets_dev, uint64_t cap,
+                        uint8_t* task_state_dev, dlsm_kv_handle* task_handle_dev, uint8_t* get_state_dev,
+                        dlsm_kv_handle* get_handle_dev);
+int dlsm_index_seek(dlsm_ctx* ctx, const dlsm_tableindex* ti, const dlsm_keyset* keys, uint64_t snapshot,
+                    const uint64_t* file_begin, const uint32_t* gets, uint64_t cap, uint8_t* task_state,
+                    dlsm_kv_handle* task_handle, uint8_t* get_state, dlsm_kv_handle* get_handle);
+/* Host only (no device touched).  dlsm_index_block_check: the open's
+ * validation of one block's contents (DLSM_OK or DLSM_E_CORRUPT).
+ * dlsm_index_block_seek: InternalGet's index step for one user key on one
+ * block's contents -- the per-Get path; it decodes only the entries it touches
+ * (bounds-checked; an entry that does not decode ends the search as NOTFOUND,
+ * as CorruptionError leaves the iterator invalid) and returns DLSM_E_CORRUPT
+ * only where Block's ctor rejects the contents. */
+int dlsm_index_block_check(const uint8_t* contents, uint64_t len, uint64_t* n_entries);
+int dlsm_index_block_seek(const uint8_t* contents, uint64_t len, const uint8_t* user_key, uint64_t key_len,
+                          uint64_t snapshot, uint32_t file, uint8_t* state, dlsm_kv_handle* handle);
+/* Entries per fence of an opened index and tasks per workgroup step of the
+ * seek (the sizes around which its tests are built). */
+uint32_t dlsm_index_fence_interval(void);
+uint32_t dlsm_index_seek_block(void);
+
 /* ---- legacy FilterPolicy format (util/bloom.cc) ------------------------- */
 
 /* CreateFilter(keys, n, dst) per job: writes bytes+1 bytes at out.

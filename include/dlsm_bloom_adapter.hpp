@@ -1528,4 +1528,157 @@ class ShardRouter {
   int last_status_ = DLSM_OK;
 };
 
+namespace host {
+
+// Table::InternalGet's index step (table/table.cc:461-510) for one user key on
+// one index block's contents: iiter->Seek(LookupKey(user_key, snapshot)), then
+// the state (DLSM_GET_*) and the BlockHandle of the pair to read.  The per-Get
+// path and the batch's fallback.  Returns DLSM_E_CORRUPT only where Block's
+// ctor rejects the contents (the reference then finds nothing either).
+inline int IndexBlockSeek(const Slice& contents, const Slice& user_key, uint64_t snapshot, uint8_t* state,
+                          dlsm_kv_handle* handle, uint32_t file = 0) {
+  return dlsm_index_block_seek(reinterpret_cast<const uint8_t*>(contents.data()), contents.size(),
+                               reinterpret_cast<const uint8_t*>(user_key.data()), user_key.size(), snapshot, file,
+                               state, handle);
+}
+
+// dlsm_index_seek's arrays from a host loop over the tasks (contents[f] empty
+// with a null pointer: no index held for f).
+inline int SeekPlan(const std::vector<Slice>& contents, const dlsm_keyset& keys, uint64_t snapshot,
+                    const uint64_t* file_begin, const uint32_t* gets, uint64_t cap, uint8_t* task_state,
+                    dlsm_kv_handle* task_handle, uint8_t* get_state, dlsm_kv_handle* get_handle) {
+  if (!file_begin || keys.n > 0xffffffffull || (keys.n && !keys.bytes) || snapshot > ((uint64_t(1) << 56) - 1))
+    return DLSM_E_ARG;
+  const size_t nf = contents.size();
+  const uint64_t limit = file_begin[nf] < cap ? file_begin[nf] : cap;
+  if (limit && !gets) return DLSM_E_ARG;
+  for (size_t f = 0; f < nf; f++) {
+    const uint64_t end = file_begin[f + 1] < limit ? file_begin[f + 1] : limit;
+    for (uint64_t t = file_begin[f]; t < end; t++) {
+      const uint64_t g = gets[t];
+      uint8_t st = DLSM_GET_NOTFOUND;
+      dlsm_kv_handle h{0, 0, 0};
+      if (g < keys.n && contents[f].data()) {
+        const uint64_t at = keys.offsets ? keys.offsets[g] : g * keys.key_len;
+        uint64_t len = keys.offsets ? keys.offsets[g + 1] - at : keys.key_len;
+        len = len > keys.suffix_len ? len - keys.suffix_len : 0;  // ExtractUserKey
+        (void)IndexBlockSeek(contents[f], Slice(reinterpret_cast<const char*>(keys.bytes) + at, len), snapshot, &st, &h,
+                             static_cast<uint32_t>(f));
+      }
+      if (task_state) task_state[t] = st;
+      if (task_handle) task_handle[t] = h;
+      if (st != DLSM_GET_NOTFOUND && g < keys.n) {
+        if (get_state) get_state[g] = st;
+        if (get_handle) get_handle[g] = h;
+      }
+    }
+  }
+  return DLSM_OK;
+}
+
+}  // namespace host
+
+// The index blocks of a version's tables (Table::rep->index_block of each):
+// FromBlocks checks every sealed block on the host (ReadFilterBlock's trailer
+// checks, then the contents' validation -- DLSM_BLOCK_INDEX where Block's ctor
+// or Seek would reject or misread them) and keeps the contents.  Seek (one key,
+// the per-Get path) is answered on the host; SeekPlan (a read plan's tasks in
+// host memory) runs on the GPU and, if the device cannot take it, in
+// host::SeekPlan with identical arrays (counted: dlsm_fallback_note).  A block
+// given as a null Slice means no index is held for that file.
+class TableIndex {
+ public:
+  static TableIndex* FromBlocks(const std::vector<Slice>& blocks, bool verify_checksums, dlsm_ctx* ctx = nullptr,
+                                std::vector<uint8_t>* status = nullptr) {
+    TableIndex* ti = new TableIndex(ctx, verify_checksums);
+    bool ok = true;
+    if (status) status->assign(blocks.size(), DLSM_BLOCK_OK);
+    for (size_t f = 0; f < blocks.size(); f++) {
+      ti->held_.push_back(blocks[f].data() != nullptr);
+      ti->blocks_.push_back(std::string(blocks[f].data() ? blocks[f].data() : "", blocks[f].size()));
+      if (!blocks[f].data()) continue;
+      Slice c;
+      int st = host::ReadFilterBlock(Slice(ti->blocks_[f].data(), ti->blocks_[f].size()), verify_checksums, &c);
+      if (st == DLSM_BLOCK_OK &&
+          dlsm_index_block_check(reinterpret_cast<const uint8_t*>(c.data()), c.size(), nullptr) != DLSM_OK)
+        st = DLSM_BLOCK_INDEX;
+      if (status) (*status)[f] = static_cast<uint8_t>(st);
+      ok = ok && st == DLSM_BLOCK_OK;
+    }
+    if (!ok) {
+      delete ti;
+      return nullptr;
+    }
+    for (size_t f = 0; f < blocks.size(); f++)  // (the strings no longer move)
+      ti->contents_.push_back(ti->held_[f] ? Slice(ti->blocks_[f].data(), ti->blocks_[f].size() - host::kBlockTrailerSize)
+                                           : Slice(nullptr, 0));
+    return ti;
+  }
+  ~TableIndex() {
+    if (dev_) dlsm_tableindex_destroy(dev_);
+  }
+  TableIndex(const TableIndex&) = delete;
+  TableIndex& operator=(const TableIndex&) = delete;
+
+  int n_files() const { return static_cast<int>(contents_.size()); }
+  // InternalGet's index step for one Get on file `file`.
+  int Seek(int file, const Slice& user_key, uint64_t snapshot, uint8_t* state, dlsm_kv_handle* handle) const {
+    if (file < 0 || file >= n_files()) return DLSM_E_ARG;
+    if (!contents_[file].data()) {
+      if (state) *state = DLSM_GET_NOTFOUND;
+      if (handle) *handle = dlsm_kv_handle{0, 0, 0};
+      return DLSM_OK;
+    }
+    return host::IndexBlockSeek(contents_[file], user_key, snapshot, state, handle, static_cast<uint32_t>(file));
+  }
+  // dlsm_index_seek on host arrays (see dlsm_index_seek_dev for the outputs).
+  int SeekPlan(const dlsm_keyset& keys, uint64_t snapshot, const uint64_t* file_begin, const uint32_t* gets,
+               uint64_t cap, uint8_t* task_state, dlsm_kv_handle* task_handle, uint8_t* get_state,
+               dlsm_kv_handle* get_handle) {
+    dlsm_ctx* ctx = ctx_ ? ctx_ : ThreadContext();
+    last_status_ = ctx ? device_seek(ctx, keys, snapshot, file_begin, gets, cap, task_state, task_handle, get_state,
+                                     get_handle)
+                       : DLSM_E_DEVICE;
+    if (last_status_ == DLSM_OK || last_status_ == DLSM_E_ARG) return last_status_;  // bad arguments stay bad
+    const int st = host::SeekPlan(contents_, keys, snapshot, file_begin, gets, cap, task_state, task_handle, get_state,
+                                  get_handle);
+    if (st == DLSM_OK) dlsm_fallback_note(ctx);
+    return st;
+  }
+  // The last SeekPlan's GPU status (the arrays are complete either way).
+  int status() const { return last_status_; }
+
+ private:
+  TableIndex(dlsm_ctx* ctx, bool verify) : ctx_(ctx), verify_(verify) {}
+  int device_seek(dlsm_ctx* ctx, const dlsm_keyset& keys, uint64_t snapshot, const uint64_t* file_begin,
+                  const uint32_t* gets, uint64_t cap, uint8_t* task_state, dlsm_kv_handle* task_handle,
+                  uint8_t* get_state, dlsm_kv_handle* get_handle) {
+    if (!file_begin) return DLSM_E_ARG;
+    if (!dev_ || dev_device_ != dlsm_ctx_device(ctx)) {
+      if (dev_) dlsm_tableindex_destroy(dev_);
+      dev_ = nullptr;
+      std::vector<const uint8_t*> p;
+      std::vector<uint64_t> l;
+      for (size_t f = 0; f < blocks_.size(); f++) {
+        p.push_back(held_[f] ? reinterpret_cast<const uint8_t*>(blocks_[f].data()) : nullptr);
+        l.push_back(blocks_[f].size());
+      }
+      const int st = dlsm_tableindex_create_blocks(ctx, p.data(), l.data(), static_cast<int>(p.size()), 0,
+                                                   verify_ ? 1 : 0, nullptr, &dev_);
+      if (st != DLSM_OK) return (st == DLSM_E_ARG || st == DLSM_E_CORRUPT) ? DLSM_E_DEVICE : st;  // (checked on the host)
+      dev_device_ = dlsm_ctx_device(ctx);
+    }
+    return dlsm_index_seek(ctx, dev_, &keys, snapshot, file_begin, gets, cap, task_state, task_handle, get_state,
+                           get_handle);
+  }
+  std::vector<std::string> blocks_;  // the sealed blocks as given
+  std::vector<bool> held_;
+  std::vector<Slice> contents_;      // each block without its trailer
+  dlsm_ctx* ctx_;
+  bool verify_;
+  dlsm_tableindex* dev_ = nullptr;
+  int dev_device_ = -1;
+  int last_status_ = DLSM_OK;
+};
+
 }  // namespace dlsm_adapter

@@ -3,8 +3,11 @@ builds against the oracle: the shapes of
 tests/test_version_probe.py::test_gpu_version_probe_random_shapes and
 tests/test_gpu_parity.py::test_full_probe_random_sets over many seeds, and
 build batches of random table counts, sizes, duplicates, bits_per_key 1-24
-and key lengths (checker only: the oracle is test infrastructure).
-    python scripts/diag_random_soak.py [SEEDS]"""
+and key lengths (checker only: the oracle is test infrastructure); and of the
+table index: random index blocks, task lists and snapshots against bisect over
+(user_key, 2**64 - 1 - trailer).
+    python scripts/diag_random_soak.py [SEEDS] [index]    (index: that leg alone)"""
+import bisect
 import os
 import sys
 import time
@@ -151,12 +154,93 @@ def internal_case(ctx, seed):
     return ok and np.array_equal(mask, want), T
 
 
+def index_case(ctx, seed):
+    """1-12 index blocks of 0-4,000 entries (crowded prefixes, up to 30 versions
+    per user key, deletions and type bytes > 1, handles of every varint
+    length), a random task list (ALL-shaped: a Get may sit in several files)
+    and snapshot: the task arrays equal bisect's answers."""
+    from dlsm_amd import index_block as ib
+
+    rng = np.random.default_rng(60_000 + seed)
+    M = 2**64 - 1
+    pre = [b"", b"0000000000000042", b"\x80" * 15 + b"\xff", b"\xff" * 16, b"L" * int(rng.integers(100, 125))]
+    alphabet = [b"\0", b"a", b"\x80", b"\xff"]
+
+    def user_key():
+        k = pre[int(rng.integers(0, len(pre)))]
+        if rng.random() < 0.15:
+            k = k[:int(rng.integers(0, 17))]
+        return k + b"".join(alphabet[int(x)] for x in rng.integers(0, 4, int(rng.integers(0, 6))))
+
+    F = int(rng.integers(1, 13))
+    tables, blocks = [], []
+    pool = [user_key() for _ in range(int(rng.integers(1, 1500)))]
+    for f in range(F):
+        if rng.random() < 0.1:
+            tables.append(None)
+            blocks.append(None)
+            continue
+        rows = set()
+        for _ in range(int(rng.integers(0, 1200))):
+            k = pool[int(rng.integers(0, len(pool)))]
+            for _ in range(int(rng.integers(1, 30)) if rng.random() < 0.1 else 1):
+                t = int(rng.integers(2, 256)) if rng.random() < 0.03 else int(rng.integers(0, 2))
+                rows.add((k, M - ((int(rng.integers(0, 1000)) << 8) | t)))
+        keys = sorted(rows)
+        handles = [(int(rng.integers(0, 1 << 62)) >> int(rng.integers(0, 62)), int(rng.integers(0, 1 << 32)) >>
+                    int(rng.integers(0, 32))) for _ in keys]
+        tables.append((keys, handles))
+        blocks.append(ib.build_index_block([k + (M - inv).to_bytes(8, "little") for k, inv in keys], handles))
+    ti = ctx.tableindex(blocks)
+    n = int(rng.integers(1, 4000))
+    lookups = [pool[int(rng.integers(0, len(pool)))] if rng.random() < 0.7 else user_key() for _ in range(n)]
+    k = dlsm_amd.Keys.pack(lookups)
+    keys_d = dlsm_amd.Keys(torch.from_numpy(k.data).cuda(), n, 0, torch.from_numpy(k.offsets.view(np.int64)).cuda())
+    per_file = [rng.integers(0, n, int(rng.integers(0, 3000))) for _ in range(F)]
+    begin = np.zeros(F + 1, dtype=np.int64)
+    begin[1:] = np.cumsum([len(p) for p in per_file])
+    gets = np.concatenate(per_file + [np.zeros(1, np.int64)]).astype(np.int32)
+    T = int(begin[-1])
+    snap = int(rng.integers(0, 1001)) if rng.random() < 0.8 else (1 << 56) - 1
+    ts = torch.full((T + 1,), 0xEE, dtype=torch.uint8, device="cuda")
+    th = torch.zeros((T + 1, 16), dtype=torch.uint8, device="cuda")
+    ctx.index_seek_dev(ti, keys_d, snap, torch.from_numpy(begin).cuda(), torch.from_numpy(gets).cuda(), cap=T,
+                       task_state=ts, task_handle=th)
+    ctx.sync()
+    want_s = np.full(T + 1, 0xEE, dtype=np.uint8)
+    want_h = np.zeros(T + 1, dtype=dlsm_amd.KV_HANDLE)
+    for f in range(F):
+        for t in range(int(begin[f]), int(begin[f + 1])):
+            want_s[t] = 0
+            if tables[f] is None:
+                continue
+            keys, handles = tables[f]
+            uk = lookups[int(gets[t])]
+            i = bisect.bisect_left(keys, (uk, M - ((snap << 8) | 1)))
+            if i == len(keys):
+                continue
+            typ = (M - keys[i][1]) & 0xFF
+            if typ > 1 or keys[i][0] == uk:
+                want_s[t] = 3 if typ > 1 else (1 if typ == 1 else 2)
+                want_h[t] = (handles[i][0], handles[i][1], f)
+    ok = np.array_equal(ts.cpu().numpy(), want_s) and \
+        np.array_equal(th.cpu().numpy().reshape(-1).view(dlsm_amd.KV_HANDLE), want_h)
+    ti.close()
+    return ok, F
+
+
 def main():
     seeds = int(sys.argv[1]) if len(sys.argv) > 1 else 100
+    only_index = len(sys.argv) > 2 and sys.argv[2] == "index"
     ctx = dlsm_amd.Context(0)
     bad = []
     t0 = time.time()
     for s in range(seeds):
+        ok, F = index_case(ctx, s)
+        if not ok:
+            bad.append(("index", s, F))
+        if only_index:
+            continue
         ok, nf = version_case(ctx, s)
         if not ok:
             bad.append(("version", s, nf))
@@ -175,9 +259,12 @@ def main():
         if s % 10 == 9:
             print(f"seed {s + 1}/{seeds}: {len(bad)} mismatches, {time.time() - t0:.0f} s", flush=True)
     ctx.close()
-    print("soak:", seeds, "version cases,", seeds, "probe cases,", seeds, "build batches (full + legacy + sealed blocks),", seeds,
-          "variable-length and", seeds, "internal-key build + probe cases, mismatches:",
-          bad, flush=True)
+    if only_index:
+        print("soak:", seeds, "table-index cases, mismatches:", bad, flush=True)
+    else:
+        print("soak:", seeds, "version cases,", seeds, "probe cases,", seeds,
+              "build batches (full + legacy + sealed blocks),", seeds, "variable-length,", seeds,
+              "internal-key build + probe and", seeds, "table-index cases, mismatches:", bad, flush=True)
     sys.exit(1 if bad else 0)
 
 
