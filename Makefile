@@ -5,10 +5,10 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -Wall -Wno-unused-result
 SRC := dlsm_amd/csrc/bloom_kernels.hip dlsm_amd/csrc/bloom_capi.hip dlsm_amd/csrc/block_crc.hip \
-       dlsm_amd/csrc/block_ingest.hip dlsm_amd/csrc/read_plan.hip dlsm_amd/csrc/shard_route.hip dlsm_amd/csrc/index_seek.hip \
+       dlsm_amd/csrc/block_ingest.hip dlsm_amd/csrc/read_plan.hip dlsm_amd/csrc/shard_route.hip dlsm_amd/csrc/index_seek.hip dlsm_amd/csrc/kv_read.hip \
        dlsm_amd/csrc/key_select.hip dlsm_amd/csrc/stream_probe.hip \
        dlsm_amd/csrc/multi_device.hip dlsm_amd/csrc/batcher.hip dlsm_amd/csrc/host_hash.hip
-HDR := dlsm_amd/csrc/bloom_math.h dlsm_amd/csrc/bloom_internal.h dlsm_amd/csrc/host_plan.h dlsm_amd/csrc/read_plan.h dlsm_amd/csrc/shard_route.h dlsm_amd/csrc/index_seek.h dlsm_amd/csrc/sort_pass.h include/dlsm_bloom.h
+HDR := dlsm_amd/csrc/bloom_math.h dlsm_amd/csrc/bloom_internal.h dlsm_amd/csrc/host_plan.h dlsm_amd/csrc/read_plan.h dlsm_amd/csrc/shard_route.h dlsm_amd/csrc/index_seek.h dlsm_amd/csrc/kv_read.h dlsm_amd/csrc/sort_pass.h include/dlsm_bloom.h
 LIB := dlsm_amd/lib/libdlsm_bloom.so
 OBJ := $(patsubst dlsm_amd/csrc/%.hip,build/%.o,$(SRC))
 

@@ -33,6 +33,7 @@ __all__ = [
     "ShardMap", "MAX_SHARDS", "ROUTE_ALIGN", "shard_route_cap", "shard_route_chunk",
     "TableIndex", "BLOCK_INDEX", "GET_NOTFOUND", "GET_FOUND", "GET_DELETED", "GET_CORRUPT", "KV_HANDLE",
     "index_fence_interval", "index_seek_block", "index_block_check", "index_block_seek",
+    "TableData", "kv_read_chunk", "kv_read_span", "kv_pair_read",
 ]
 
 PATH_AUTO, PATH_DIRECT, PATH_SLICED = 0, 1, 2
@@ -104,6 +105,32 @@ def index_block_seek(contents: bytes, user_key: bytes, snapshot: int, file: int 
     check(lib().dlsm_index_block_seek(a.ctypes.data, len(contents), k.ctypes.data, len(user_key), snapshot, file,
                                       C.byref(st), C.byref(h)), "index_block_seek")
     return int(st.value), int(h.offset), int(h.size), int(h.file)
+
+
+def kv_read_chunk() -> int:
+    """Items per workgroup chunk of the value read's size pass."""
+    return int(lib().dlsm_kv_read_chunk())
+
+
+def kv_read_span() -> int:
+    """Output bytes per workgroup step of the value read's copy."""
+    return int(lib().dlsm_kv_read_span())
+
+
+def kv_pair_read(chunks, handle, user_key: bytes, state: int = GET_FOUND):
+    """The value read of one Get on the host: ``chunks`` are one file's data
+    chunks (bytes each, in offset order), ``handle`` is (offset, size[, file]).
+    Returns (state, value) with value None unless the state is GET_FOUND."""
+    keep = [np.frombuffer(bytes(c) + b"\0", dtype=np.uint8) for c in chunks]
+    ca = (_L.dlsm_data_chunk * max(len(keep), 1))(*[_L.dlsm_data_chunk(a.ctypes.data, a.size - 1) for a in keep])
+    h = _L.dlsm_kv_handle(int(handle[0]), int(handle[1]), int(handle[2]) if len(handle) > 2 else 0)
+    k = np.frombuffer(bytes(user_key) + b"\0", dtype=np.uint8)
+    st, v, vl = C.c_uint8(state), C.c_void_p(), C.c_uint32()
+    check(lib().dlsm_kv_pair_read(ca, len(keep), C.byref(h), k.ctypes.data, len(user_key), C.byref(st), C.byref(v),
+                                  C.byref(vl)), "kv_pair_read")
+    if st.value != GET_FOUND:
+        return int(st.value), None
+    return GET_FOUND, C.string_at(v.value, vl.value) if vl.value else b""
 
 
 def shard_route_cap(n: int, n_shards: int) -> int:
@@ -401,6 +428,48 @@ class TableIndex:
     def close(self):
         if getattr(self, "h", None):
             lib().dlsm_tableindex_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+class TableData:
+    """The data regions of a version's tables on one device (dlsm_tabledata):
+    ``files[f]`` is the list of file f's data chunks in offset order (bytes
+    each, or device uint8 tensors with on_device, which are referenced in
+    place and kept alive here), or None / an empty list for a file whose data
+    is not held."""
+
+    def __init__(self, ctx: "Context", files, on_device: bool = False):
+        n = len(files)
+        begin = np.zeros(n + 1, dtype=np.uint32)
+        keep, recs = [], []
+        for f, chunks in enumerate(files):
+            for c in (chunks or []):
+                if on_device:
+                    keep.append(c)
+                    recs.append(_L.dlsm_data_chunk(_ptr(c) if c.numel() else None, int(c.numel())))
+                else:
+                    a = np.frombuffer(bytes(c) + b"\0", dtype=np.uint8)
+                    keep.append(a)
+                    recs.append(_L.dlsm_data_chunk(a.ctypes.data, a.size - 1))
+            begin[f + 1] = len(recs)
+        ca = (_L.dlsm_data_chunk * max(len(recs), 1))(*recs)
+        h = C.c_void_p()
+        st = lib().dlsm_tabledata_create(ctx.h, ca, begin.ctypes.data_as(C.POINTER(C.c_uint32)), n,
+                                         1 if on_device else 0, C.byref(h))
+        self.h = h if st == _L.DLSM_OK else None
+        check(st, "tabledata_create")
+        self._keep = keep if on_device else None
+        self.n_files = n
+        nf, nc, nb = C.c_int(), C.c_uint64(), C.c_uint64()
+        check(lib().dlsm_tabledata_size(h, C.byref(nf), C.byref(nc), C.byref(nb)), "tabledata_size")
+        self.n_chunks, self.device_bytes = int(nc.value), int(nb.value)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().dlsm_tabledata_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -832,6 +901,66 @@ class Context:
         check(lib().dlsm_index_seek_dev(self.h, ti.h, C.byref(ks), snapshot, _ptr(file_begin), _ptr(gets), cap,
                                         _ptr(task_state), _ptr(task_handle), _ptr(get_state), _ptr(get_handle)),
               "index_seek_dev")
+
+    # -- value read: the tail of Table::InternalGet ------------------------------
+    def tabledata(self, files, on_device: bool = False) -> TableData:
+        return TableData(self, files, on_device)
+
+    def kv_read_dev(self, td: TableData, keys: Keys, state, handle, value_off, values, *, gets=None, count=None,
+                    cap: Optional[int] = None, values_cap: Optional[int] = None, n_corrupt=None):
+        """Read the values of a seeked batch: state (device uint8[cap], updated
+        in place) and handle (device, 16 bytes per item: KV_HANDLE) are the
+        seek's per-Get arrays, or its per-task arrays with gets (device
+        uint32[cap]: each item's key index) and count (a device uint64: the
+        item count, e.g. file_begin[n_files:]).  value_off (device uint64[cap +
+        1]) gets the values' exclusive byte offsets and the total, values
+        (device uint8, 16-byte aligned) the bytes below min(total, values_cap);
+        n_corrupt (device uint64[1]) the items set to GET_CORRUPT.
+        Asynchronous; cap defaults to state's length, values_cap to values'."""
+        cap = (0 if state is None else int(state.numel())) if cap is None else int(cap)
+        values_cap = _nbytes(values) if values_cap is None else int(values_cap)
+        _need(state, cap, "state")
+        _need(handle, 16 * cap, "handle")
+        _need(value_off, 8 * (cap + 1) if cap else 0, "value_off")
+        _need(values, values_cap, "values")
+        for x, nb, what in ((gets, 4 * cap, "gets"), (count, 8, "count"), (n_corrupt, 8, "n_corrupt")):
+            if x is not None:
+                _need(x, nb, what)
+        ks = keys.c()
+        check(lib().dlsm_kv_read_dev(self.h, td.h, C.byref(ks), _ptr(gets), _ptr(count), cap, _ptr(state), _ptr(handle),
+                                     _ptr(value_off), _ptr(values), values_cap, _ptr(n_corrupt)), "kv_read_dev")
+
+    def kv_read_stats(self):
+        """(size, offsets, copy) device milliseconds of the last kv_read_dev
+        (call after sync) and the copy's grid in workgroups."""
+        ms, wgs = (C.c_double * 3)(), C.c_uint32()
+        check(lib().dlsm_kv_read_stats(self.h, ms, C.byref(wgs)), "kv_read_stats")
+        return (float(ms[0]), float(ms[1]), float(ms[2])), int(wgs.value)
+
+    def kv_read(self, td: TableData, keys: Keys, state: np.ndarray, handle: np.ndarray, *, gets=None,
+                count: Optional[int] = None, values_cap: int = 0):
+        """The host-memory form: state (uint8[cap], updated in place), handle
+        (KV_HANDLE[cap]).  Returns (value_off uint64[m + 1], values uint8,
+        n_corrupt)."""
+        if not isinstance(state, np.ndarray) or state.dtype != np.uint8 or not state.flags.c_contiguous:
+            raise ValueError("state: a contiguous numpy uint8 array is needed")
+        cap = int(state.size)
+        if not isinstance(handle, np.ndarray) or handle.dtype.itemsize != 16 or not handle.flags.c_contiguous:
+            raise ValueError("handle: a contiguous numpy array of 16-byte records (KV_HANDLE) is needed")
+        _need(handle, 16 * cap, "handle")
+        if gets is not None:
+            if not isinstance(gets, np.ndarray) or gets.dtype != np.uint32 or not gets.flags.c_contiguous:
+                raise ValueError("gets: a contiguous numpy uint32 array is needed")
+            _need(gets, 4 * cap, "gets")
+        m = cap if count is None else min(int(count), cap)
+        cnt = None if count is None else np.array([count], dtype=np.uint64)
+        value_off = np.zeros(cap + 1, dtype=np.uint64)
+        values = np.zeros(max(values_cap, 1), dtype=np.uint8)
+        bad = np.zeros(1, dtype=np.uint64)
+        ks = keys.c()
+        check(lib().dlsm_kv_read(self.h, td.h, C.byref(ks), _ptr(gets), _ptr(cnt), cap, _ptr(state), _ptr(handle),
+                                 _ptr(value_off), _ptr(values), values_cap, _ptr(bad)), "kv_read")
+        return value_off[:m + 1], values[:min(int(value_off[m]), values_cap)], int(bad[0])
 
     # -- full filter probe --------------------------------------------------
     def filterset(self, filters, on_device: bool = False, *, sealed: bool = False,

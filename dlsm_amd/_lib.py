@@ -53,6 +53,10 @@ class dlsm_kv_handle(C.Structure):
     _fields_ = [("offset", C.c_uint64), ("size", C.c_uint32), ("file", C.c_uint32)]
 
 
+class dlsm_data_chunk(C.Structure):
+    _fields_ = [("base", C.c_void_p), ("len", C.c_uint64)]
+
+
 class DlsmError(RuntimeError):
     def __init__(self, status: int, what: str = ""):
         self.status = status
@@ -171,6 +175,19 @@ SIGNATURES = [
                                         C.POINTER(C.c_uint8), C.POINTER(dlsm_kv_handle)]),
     ("dlsm_index_fence_interval", C.c_uint32, []),
     ("dlsm_index_seek_block", C.c_uint32, []),
+    ("dlsm_tabledata_create", C.c_int, [_VP, C.POINTER(dlsm_data_chunk), C.POINTER(C.c_uint32), C.c_int, C.c_int,
+                                        C.POINTER(_VP)]),
+    ("dlsm_tabledata_destroy", C.c_int, [_VP]),
+    ("dlsm_tabledata_size", C.c_int, [_VP, C.POINTER(C.c_int), _U64P, _U64P]),
+    ("dlsm_kv_read_dev", C.c_int, [_VP, _VP, C.POINTER(dlsm_keyset), _VP, _VP, C.c_uint64, _VP, _VP, _VP, _VP,
+                                   C.c_uint64, _VP]),
+    ("dlsm_kv_read", C.c_int, [_VP, _VP, C.POINTER(dlsm_keyset), _VP, _VP, C.c_uint64, _VP, _VP, _VP, _VP,
+                               C.c_uint64, _VP]),
+    ("dlsm_kv_pair_read", C.c_int, [C.POINTER(dlsm_data_chunk), C.c_uint32, C.POINTER(dlsm_kv_handle), _VP, C.c_uint64,
+                                    C.POINTER(C.c_uint8), C.POINTER(_VP), C.POINTER(C.c_uint32)]),
+    ("dlsm_kv_read_chunk", C.c_uint32, []),
+    ("dlsm_kv_read_span", C.c_uint32, []),
+    ("dlsm_kv_read_stats", C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
     ("dlsm_bloom_full_probe", C.c_int, [_VP, _VP, C.POINTER(dlsm_keyset), _VP]),
     ("dlsm_bloom_full_probe_hashed_dev", C.c_int, [_VP, _VP, C.POINTER(dlsm_keyset), _VP]),
     ("dlsm_bloom_hash_batch", C.c_int, [C.POINTER(dlsm_keyset), _VP, C.c_int]),

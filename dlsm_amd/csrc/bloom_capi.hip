@@ -157,6 +157,10 @@ struct dlsm_ctx {
   DevBuf<uint8_t> smask;
   DevBuf<uint8_t> plan_ws;  // read plan: tables and intermediate pairs (plan::ReadPlan's layout)
   DevBuf<uint8_t> route_ws;  // shard route: the Gets' bins and the tables (plan::ShardRoute's layout)
+  DevBuf<uint8_t> kv_ws;     // value read: lengths, source addresses, partial sums (plan::KvReadPlan's layout)
+  hipEvent_t ev_kv[4] = {};  // value read: around its three launches (dlsm_kv_read_stats)
+  bool kv_timed = false;     // the last dlsm_kv_read_dev recorded all four
+  int cus = 0;               // the device's compute units (0: not asked yet)
   // host-API staging
   DevBuf<uint8_t> st_keys;
   DevBuf<uint64_t> st_offs;
@@ -584,6 +588,7 @@ int dlsm_ctx_destroy(dlsm_ctx* ctx) {
   ctx->smask.release();
   ctx->plan_ws.release();
   ctx->route_ws.release();
+  ctx->kv_ws.release();
   ctx->sel.release();
   ctx->st_keys.release();
   ctx->st_offs.release();
@@ -600,6 +605,8 @@ int dlsm_ctx_destroy(dlsm_ctx* ctx) {
   ctx->ing_part0.release();
   ctx->ing_partial.release();
   ctx->ing_rec.release();
+  for (hipEvent_t e : ctx->ev_kv)
+    if (e) (void)hipEventDestroy(e);
   if (ctx->ev_ing0) (void)hipEventDestroy(ctx->ev_ing0);
   if (ctx->ev_ing1) (void)hipEventDestroy(ctx->ev_ing1);
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
@@ -809,7 +816,7 @@ int dlsm_ctx_stats(dlsm_ctx* ctx, uint64_t* device_allocs, uint64_t* device_byte
   add(ctx->vgl); add(ctx->vabyte); add(ctx->vplan); add(ctx->plan_ws); add(ctx->route_ws);
   add(ctx->st_keys); add(ctx->st_offs); add(ctx->st_out); add(ctx->st_len); add(ctx->st_filter);
   add(ctx->crc_streams); add(ctx->crc_partial); add(ctx->crc_tabs); add(ctx->crc_outp); add(ctx->crc_cap);
-  add(ctx->crc_val); add(ctx->sel);
+  add(ctx->crc_val); add(ctx->sel); add(ctx->kv_ws);
   if (device_allocs) *device_allocs = n;
   if (device_bytes) *device_bytes = b;
   return DLSM_OK;
@@ -2806,6 +2813,231 @@ int dlsm_index_seek(dlsm_ctx* ctx, const dlsm_tableindex* ti, const dlsm_keyset*
   if (get_state && n) DLSM_TRY(hipMemcpyAsync(get_state, st + gso, n, hipMemcpyDeviceToHost, s));
   if (get_handle && n) DLSM_TRY(hipMemcpyAsync(get_handle, st + gho, 16 * n, hipMemcpyDeviceToHost, s));
   DLSM_TRY(ctx_sync(ctx, s));
+  return DLSM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Value read: the tail of Table::InternalGet (table/table.cc:482-508) for a
+// seeked Get batch (kv_read.hip)
+// ---------------------------------------------------------------------------
+struct dlsm_tabledata {
+  int device = 0;
+  int n_files = 0;
+  uint64_t n_chunks = 0;
+  uint64_t bytes = 0;
+  uint8_t* tables = nullptr;  // [chunk_begin | end | base], each region 256-byte aligned
+  uint8_t* arena = nullptr;   // host chunks' copies
+  KvTables t{};
+};
+
+int dlsm_tabledata_create(dlsm_ctx* ctx, const dlsm_data_chunk* chunks, const uint32_t* chunk_begin, int n_files,
+                          int chunks_are_device, dlsm_tabledata** out) {
+  if (!out) return DLSM_E_ARG;
+  *out = nullptr;
+  if (!ctx || n_files < 0) return DLSM_E_ARG;
+  TableDataPlan P;
+  DLSM_CHECK(plan_tabledata(chunks, chunk_begin, n_files, P));
+  if (ctx->fault) return -ctx->fault;
+  DeviceGuard g(ctx->device);
+  dlsm_tabledata* td = new (std::nothrow) dlsm_tabledata();
+  if (!td) return DLSM_E_NOMEM;
+  td->device = ctx->device;
+  td->n_files = n_files;
+  td->n_chunks = P.end.size();
+  const uint64_t nc = td->n_chunks;
+  auto run = [&]() -> int {
+    hipStream_t s = ctx->stream;
+    Layout L;
+    const uint64_t bo = L.take(sizeof(uint32_t) * (static_cast<uint64_t>(n_files) + 1)), eo = L.take(sizeof(uint64_t) * nc),
+                   po = L.take(sizeof(uint8_t*) * nc);
+    DLSM_TRY(hipMalloc(reinterpret_cast<void**>(&td->tables), L.at));
+    if (!chunks_are_device) DLSM_TRY(hipMalloc(reinterpret_cast<void**>(&td->arena), std::max<uint64_t>(P.arena_bytes, 256)));
+    td->bytes = L.at + (chunks_are_device ? 0 : P.arena_bytes);
+    std::vector<const uint8_t*> base(nc);
+    for (uint64_t c = 0; c < nc; c++) {
+      base[c] = chunks[c].base;
+      if (chunks_are_device) continue;
+      base[c] = td->arena + P.arena_off[c];
+      if (chunks[c].len)
+        DLSM_TRY(hipMemcpyAsync(td->arena + P.arena_off[c], chunks[c].base, chunks[c].len, hipMemcpyHostToDevice, s));
+    }
+    DLSM_CHECK(ctx_upload(ctx, td->tables + bo, chunk_begin, sizeof(uint32_t) * (static_cast<uint64_t>(n_files) + 1), s));
+    DLSM_CHECK(ctx_upload(ctx, td->tables + eo, P.end.data(), sizeof(uint64_t) * nc, s));
+    DLSM_CHECK(ctx_upload(ctx, td->tables + po, base.data(), sizeof(uint8_t*) * nc, s));
+    DLSM_TRY(ctx_sync(ctx, s));  // the caller's host chunks are free again
+    td->t.chunk_begin = reinterpret_cast<const uint32_t*>(td->tables + bo);
+    td->t.end = reinterpret_cast<const uint64_t*>(td->tables + eo);
+    td->t.base = reinterpret_cast<const uint8_t* const*>(td->tables + po);
+    td->t.n_files = static_cast<uint32_t>(n_files);
+    return DLSM_OK;
+  };
+  const int ret = run();
+  if (ret != DLSM_OK) {
+    dlsm_tabledata_destroy(td);
+    return ret;
+  }
+  *out = td;
+  return DLSM_OK;
+}
+
+int dlsm_tabledata_destroy(dlsm_tabledata* td) {
+  if (!td) return DLSM_OK;
+  DeviceGuard g(td->device);
+  if (td->arena) (void)hipFree(td->arena);
+  if (td->tables) (void)hipFree(td->tables);
+  delete td;
+  return DLSM_OK;
+}
+
+int dlsm_tabledata_size(const dlsm_tabledata* td, int* n_files, uint64_t* n_chunks, uint64_t* device_bytes) {
+  if (!td) return DLSM_E_ARG;
+  if (n_files) *n_files = td->n_files;
+  if (n_chunks) *n_chunks = td->n_chunks;
+  if (device_bytes) *device_bytes = td->bytes;
+  return DLSM_OK;
+}
+
+uint32_t dlsm_kv_read_chunk(void) { return kKvChunk; }
+uint32_t dlsm_kv_read_span(void) { return kKvSpan; }
+
+int dlsm_kv_pair_read(const dlsm_data_chunk* chunks, uint32_t n_chunks, const dlsm_kv_handle* handle,
+                      const uint8_t* user_key, uint64_t key_len, uint8_t* state, const uint8_t** value,
+                      uint32_t* value_len) {
+  if (value) *value = nullptr;
+  if (value_len) *value_len = 0;
+  if (!state || !handle || (!chunks && n_chunks) || (!user_key && key_len) || key_len > 0xffffffffull) return DLSM_E_ARG;
+  if (*state != DLSM_GET_FOUND) return DLSM_OK;
+  std::vector<uint64_t> end(n_chunks);
+  std::vector<const uint8_t*> base(n_chunks);
+  uint64_t at = 0;
+  for (uint32_t c = 0; c < n_chunks; c++) {
+    if ((chunks[c].len && !chunks[c].base) || at + chunks[c].len < at) return DLSM_E_ARG;
+    end[c] = at += chunks[c].len;
+    base[c] = chunks[c].base;
+  }
+  const uint8_t* v = nullptr;
+  uint32_t vl = 0;
+  const uint8_t* p = kv_pair_locate(KvChunks{end.data(), base.data(), n_chunks}, handle->offset, handle->size);
+  *state = p ? kv_pair_decide(p, handle->size, user_key, static_cast<uint32_t>(key_len), &v, &vl) : kGetCorrupt;
+  if (value) *value = v;
+  if (value_len) *value_len = vl;
+  return DLSM_OK;
+}
+
+int dlsm_kv_read_dev(dlsm_ctx* ctx, const dlsm_tabledata* td, const dlsm_keyset* keys, const uint32_t* gets_dev,
+                     const uint64_t* count_dev, uint64_t cap, uint8_t* state_dev, const dlsm_kv_handle* handle_dev,
+                     uint64_t* value_off_dev, uint8_t* values_dev, uint64_t values_cap, uint64_t* n_corrupt_dev) {
+  if (!ctx || !td || !keys || td->device != ctx->device) return DLSM_E_ARG;
+  DLSM_CHECK(validate_keyset(*keys));
+  KvReadPlan P;
+  DLSM_CHECK(plan_kv_read(cap, kSortMaxWgs, kKvCopyWgs, P));  // (the copy's grid: below, once the device is known)
+  if (keys->n > 0xffffffffull) return DLSM_E_ARG;
+  if (cap > 0 && (!state_dev || !handle_dev || !value_off_dev || (values_cap > 0 && !values_dev))) return DLSM_E_ARG;
+  if (!aligned(values_dev, 16) || !aligned(handle_dev, 8) || !aligned(value_off_dev, 8) || !aligned(count_dev, 8) ||
+      !aligned(gets_dev, 4) || !aligned(n_corrupt_dev, 8))
+    return DLSM_E_ARG;
+  if (ctx->fault) return -ctx->fault;
+  if (cap == 0) return DLSM_OK;
+  DeviceGuard g(ctx->device);
+  if (!ctx->cus) {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || cus <= 0)
+      cus = kKvCopyWgs / kKvCopyWgsPerCu;
+    ctx->cus = cus;
+  }
+  P.copy_wgs = plan_kv_copy_wgs(static_cast<uint32_t>(ctx->cus));
+  for (hipEvent_t& e : ctx->ev_kv)
+    if (!e) DLSM_TRY(hipEventCreate(&e));
+  ctx->kv_timed = false;
+  DLSM_CHECK(ctx->kv_ws.ensure(P.bytes));
+  uint8_t* ws = ctx->kv_ws.p;
+  KvReadDev a{};
+  a.tables = td->t;
+  a.keys = to_desc(*keys);
+  a.gets = gets_dev;
+  a.count = count_dev;
+  a.cap = cap;
+  a.state = state_dev;
+  a.handle = reinterpret_cast<const KvHandle*>(handle_dev);
+  a.value_off = value_off_dev;
+  a.values = values_dev;
+  a.values_cap = values_cap;
+  a.n_corrupt = n_corrupt_dev;
+  a.len = reinterpret_cast<uint32_t*>(ws + P.len_off);
+  a.src = reinterpret_cast<uint64_t*>(ws + P.src_off);
+  a.wg_sum = reinterpret_cast<uint64_t*>(ws + P.sum_off);
+  a.wg_bad = reinterpret_cast<uint64_t*>(ws + P.bad_off);
+  a.cpw = P.cpw;
+  a.nwg = P.nwg;
+  DLSM_TRY(launch_kv_read(a, P.copy_wgs, ctx->ev_kv, ctx->stream));
+  ctx->kv_timed = true;
+  return DLSM_OK;
+}
+
+int dlsm_kv_read_stats(const dlsm_ctx* ctx, double* launch_ms, uint32_t* copy_wgs) {
+  if (!ctx) return DLSM_E_ARG;
+  if (copy_wgs) *copy_wgs = ctx->cus ? plan_kv_copy_wgs(static_cast<uint32_t>(ctx->cus)) : 0;
+  if (launch_ms) {
+    launch_ms[0] = launch_ms[1] = launch_ms[2] = 0;
+    if (!ctx->kv_timed) return DLSM_OK;
+    DeviceGuard g(ctx->device);
+    for (int j = 0; j < 3; j++) {
+      float ms = 0;
+      DLSM_TRY(hipEventElapsedTime(&ms, ctx->ev_kv[j], ctx->ev_kv[j + 1]));
+      launch_ms[j] = ms;
+    }
+  }
+  return DLSM_OK;
+}
+
+int dlsm_kv_read(dlsm_ctx* ctx, const dlsm_tabledata* td, const dlsm_keyset* keys, const uint32_t* gets,
+                 const uint64_t* count, uint64_t cap, uint8_t* state, const dlsm_kv_handle* handle,
+                 uint64_t* value_off, uint8_t* values, uint64_t values_cap, uint64_t* n_corrupt) {
+  if (!ctx || !td || !keys || td->device != ctx->device || cap > 0xffffffffull) return DLSM_E_ARG;
+  DLSM_CHECK(validate_keyset(*keys));
+  if (keys->n > 0xffffffffull) return DLSM_E_ARG;
+  const uint64_t m = count ? std::min(*count, cap) : cap;
+  if (cap > 0 && (!value_off || (m > 0 && (!state || !handle)) || (values_cap > 0 && !values))) return DLSM_E_ARG;
+  if (ctx->fault) return -ctx->fault;
+  if (cap == 0) return DLSM_OK;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = ctx->stream;
+  const dlsm_keyset* sets[1] = {keys};
+  std::vector<dlsm_keyset> dk;
+  DLSM_CHECK(stage_keys(ctx, sets, 1, dk));
+  // staging: [gets | states | handles | value_off | corrupt count | values]; the call runs on the m items
+  Layout L;
+  const uint64_t go = L.take(4 * m), so = L.take(m), ho = L.take(16 * m), vo = L.take(8 * (m + 1)), co = L.take(8),
+                 bo = L.take(values_cap);
+  DLSM_CHECK(ctx->st_out.ensure(L.at + 256));
+  uint8_t* st = ctx->st_out.p;
+  if (m) {
+    if (gets) DLSM_TRY(hipMemcpyAsync(st + go, gets, 4 * m, hipMemcpyHostToDevice, s));
+    DLSM_TRY(hipMemcpyAsync(st + so, state, m, hipMemcpyHostToDevice, s));
+    DLSM_TRY(hipMemcpyAsync(st + ho, handle, 16 * m, hipMemcpyHostToDevice, s));
+  }
+  uint64_t total = 0;
+  if (m) {
+    DLSM_CHECK(dlsm_kv_read_dev(ctx, td, &dk[0], gets ? reinterpret_cast<uint32_t*>(st + go) : nullptr, nullptr, m, st + so,
+                                reinterpret_cast<dlsm_kv_handle*>(st + ho), reinterpret_cast<uint64_t*>(st + vo), st + bo,
+                                values_cap, reinterpret_cast<uint64_t*>(st + co)));
+    DLSM_TRY(hipMemcpyAsync(value_off, st + vo, 8 * (m + 1), hipMemcpyDeviceToHost, s));
+    if (n_corrupt) DLSM_TRY(hipMemcpyAsync(n_corrupt, st + co, 8, hipMemcpyDeviceToHost, s));
+    DLSM_TRY(ctx_sync(ctx, s));
+    total = value_off[m];
+  } else {
+    value_off[0] = 0;
+    if (n_corrupt) *n_corrupt = 0;
+  }
+  const uint64_t nb = std::min(total, values_cap);
+  if (nb) DLSM_TRY(hipMemcpyAsync(values, st + bo, nb, hipMemcpyDeviceToHost, s));
+  // the states, the call's only in-out array, are replaced once nothing can
+  // fail any more: a caller that re-runs a failed call on the host (the
+  // adapter) still holds the incoming ones
+  std::vector<uint8_t> new_state(m);
+  if (m) DLSM_TRY(hipMemcpyAsync(new_state.data(), st + so, m, hipMemcpyDeviceToHost, s));
+  if (nb || m) DLSM_TRY(ctx_sync(ctx, s));
+  if (m) memcpy(state, new_state.data(), m);
   return DLSM_OK;
 }
 

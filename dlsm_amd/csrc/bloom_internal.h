@@ -7,6 +7,7 @@
 
 #include "bloom_math.h"
 #include "index_seek.h"
+#include "kv_read.h"
 #include "read_plan.h"
 #include "shard_route.h"
 
@@ -493,5 +494,30 @@ struct IndexSeekDev {
 hipError_t launch_index_open(IndexFileDev* files, const IngestRecord* rec, const uint64_t* slot0, uint32_t n_files,
                              uint64_t slots, RoutePrefix* fence, hipStream_t s);
 hipError_t launch_index_seek(const IndexSeekDev& a, uint32_t nwg, hipStream_t s);
+
+// kv_read.hip: the value read of a seeked Get batch (dlsm_kv_read_dev).  The
+// size pass leaves each item's value length and source address in the
+// workspace (plan::KvReadPlan's layout), the offset pass turns the lengths into
+// value_off, the copy gathers the bytes.
+struct KvReadDev {
+  KvTables tables;
+  KeyDesc keys;
+  const uint32_t* gets;      // u32[cap] or nullptr: item i's key is key i
+  const uint64_t* count;     // device item count or nullptr: cap
+  uint64_t cap;
+  uint8_t* state;            // u8[cap], updated in place
+  const KvHandle* handle;    // [cap]
+  uint64_t* value_off;       // u64[cap + 1]
+  uint8_t* values;           // 16-byte aligned
+  uint64_t values_cap;
+  uint64_t* n_corrupt;       // or nullptr
+  uint32_t* len;             // workspace u32[cap]: the items' value lengths
+  uint64_t* src;             // workspace u64[cap]: the values' source addresses
+  uint64_t* wg_sum;          // workspace u64[nwg]: the size pass's length sum per workgroup
+  uint64_t* wg_bad;          // workspace u64[nwg]: items it set to CORRUPT
+  uint32_t cpw, nwg;         // plan::sort_grid(cap, kKvChunk, kSortMaxWgs)
+};
+// ev: four events recorded around the three launches, or nullptr.
+hipError_t launch_kv_read(const KvReadDev& a, uint32_t copy_wgs, hipEvent_t* ev, hipStream_t s);
 
 }  // namespace dlsm

@@ -960,5 +960,69 @@ inline uint32_t plan_index_seek_wgs(uint64_t cap, uint32_t max_wgs) {
   return static_cast<uint32_t>(std::min<uint64_t>(std::max<uint64_t>(w, 1), max_wgs));
 }
 
+// ---- value read (kv_read.hip) ---------------------------------------------------
+// dlsm_kv_read_dev from the capacity alone (the item count is read on the
+// device): the size and offset passes on sort_grid's grid of kKvChunk items, so
+// at most max_wgs (the ABI: kSortMaxWgs) workgroups share the partial-sum table,
+// the copy's persistent grid, and the workspace layout (byte offsets, every
+// region 256-byte aligned): 12 bytes per item plus the partial sums.
+struct KvReadPlan : SortGrid {
+  uint32_t copy_wgs = 0;
+  uint64_t len_off = 0, len_bytes = 0;  // u32[cap]
+  uint64_t src_off = 0, src_bytes = 0;  // u64[cap]
+  uint64_t sum_off = 0, sum_bytes = 0;  // u64[nwg]
+  uint64_t bad_off = 0, bad_bytes = 0;  // u64[nwg]
+  uint64_t bytes = 0;
+};
+
+// The copy's grid on a device of `cus` compute units.
+inline uint32_t plan_kv_copy_wgs(uint32_t cus) { return std::max<uint32_t>(cus, 1) * kKvCopyWgsPerCu; }
+
+inline int plan_kv_read(uint64_t cap, uint32_t max_wgs, uint32_t copy_wgs, KvReadPlan& P) {
+  if (cap > 0xffffffffull || max_wgs == 0 || copy_wgs == 0) return DLSM_E_ARG;
+  P = KvReadPlan();
+  static_cast<SortGrid&>(P) = sort_grid(cap, kKvChunk, max_wgs);
+  P.copy_wgs = copy_wgs;
+  Layout ws;
+  ws.region(&P.len_off, &P.len_bytes, sizeof(uint32_t) * cap);
+  ws.region(&P.src_off, &P.src_bytes, sizeof(uint64_t) * cap);
+  ws.region(&P.sum_off, &P.sum_bytes, sizeof(uint64_t) * P.nwg);
+  ws.region(&P.bad_off, &P.bad_bytes, sizeof(uint64_t) * P.nwg);
+  P.bytes = ws.at;
+  return DLSM_OK;
+}
+
+// dlsm_tabledata_create from the chunk table alone: the running ends of every
+// file's chunks (end[c] within its file), and, for host chunks, each chunk's
+// place in the arena (16-byte aligned).
+struct TableDataPlan {
+  std::vector<uint64_t> end;        // per chunk
+  std::vector<uint64_t> arena_off;  // per chunk
+  uint64_t arena_bytes = 0, data_bytes = 0;
+};
+
+inline int plan_tabledata(const dlsm_data_chunk* chunks, const uint32_t* chunk_begin, int n_files, TableDataPlan& P) {
+  if (n_files < 0 || !chunk_begin || chunk_begin[0] != 0) return DLSM_E_ARG;
+  P = TableDataPlan();
+  const uint32_t nc = chunk_begin[n_files];
+  if (nc > 0 && !chunks) return DLSM_E_ARG;
+  P.end.assign(nc, 0);
+  P.arena_off.assign(nc, 0);
+  for (int f = 0; f < n_files; f++) {
+    if (chunk_begin[f + 1] < chunk_begin[f] || chunk_begin[f + 1] > nc) return DLSM_E_ARG;
+    uint64_t at = 0;
+    for (uint32_t c = chunk_begin[f]; c < chunk_begin[f + 1]; c++) {
+      if (chunks[c].len && !chunks[c].base) return DLSM_E_ARG;
+      if (at + chunks[c].len < at) return DLSM_E_ARG;
+      at += chunks[c].len;
+      P.end[c] = at;
+      P.arena_off[c] = P.arena_bytes;
+      P.arena_bytes += (chunks[c].len + 15) & ~uint64_t(15);
+      P.data_bytes += chunks[c].len;
+    }
+  }
+  return DLSM_OK;
+}
+
 }  // namespace plan
 }  // namespace dlsm

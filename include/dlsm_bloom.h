@@ -633,7 +633,7 @@ uint32_t dlsm_shard_route_chunk(void);
  * compare, and only then the read of the pair the handle names.  These calls
  * are that step for the tasks of a read plan, so probe -> plan(FIRST) -> seek
  * -> advance runs on the device with no host read in the loop body.  The reads
- * of the values stay with the caller.
+ * of the values are dlsm_kv_read_dev's (below).
  *
  * dlsm_tableindex_create_blocks: blocks[f] (lens[f] bytes) is file f's sealed
  * index block, [contents][type 0][masked crc32c] (table_builder_bacs.cpp:
@@ -725,6 +725,93 @@ int dlsm_index_block_seek(const uint8_t* contents, uint64_t len, const uint8_t* 
  * seek (the sizes around which its tests are built). */
 uint32_t dlsm_index_fence_interval(void);
 uint32_t dlsm_index_seek_block(void);
+
+/* ---- value read: the tail of Table::InternalGet -------------------------- */
+
+/* What follows the index step for a byte-addressable table (table/table.cc:
+ * 482-508): ReadKVPair of the pair the handle names (table/format.cc:225-301,
+ * the data chunk picked by Find_Remote_MR, format.cc:63-75), the two Fixed32
+ * lengths in front of it (TableBuilder_BACS::Add, table_builder_bacs.cpp:221-226),
+ * SaveValue on the pair's own key and value->assign (db/version_set.h:61-75) --
+ * for a whole batch: (state, handle) per Get in, one packed value buffer with
+ * offsets out, byte-exact, no host read.
+ *
+ * dlsm_tabledata_create: the data regions of the version's files.  File f's
+ * data is chunks[chunk_begin[f] .. chunk_begin[f + 1]) in offset order (f: the
+ * numbering of dlsm_kv_handle.file); chunk c of a file covers the offsets
+ * [end[c - 1], end[c]), end[c] the running sum of the lengths, end[-1] = 0.  An
+ * empty range: no data is held for f.  Device chunks are referenced in place
+ * (the caller keeps them alive); host chunks are copied once into one arena.
+ * chunk_begin[0] must be 0 and the entries ascend; a chunk with len > 0 has a
+ * base.
+ *
+ * dlsm_kv_read_dev, item i < m = min(*count_dev, cap) (count_dev == NULL: cap):
+ *   its key is keys[gets_dev[i]] (the per-task arrays of an ALL plan), or key i
+ *   when gets_dev is NULL (the per-Get arrays); user keys, or internal keys
+ *   with suffix_len = 8 of which ExtractUserKey is used;
+ *   state_dev[i] other than DLSM_GET_FOUND passes through with length 0; the
+ *   handle is never dereferenced;
+ *   a FOUND item becomes DLSM_GET_CORRUPT with length 0 unless all of these
+ *   hold: its key index is below keys->n; handle.file < n_files and data is
+ *   held for the file; a chunk c with end[c] > offset exists (upper_bound: an
+ *   offset equal to a chunk's end belongs to the next chunk) and offset + size
+ *   <= end[c] (a pair never straddles chunks: the builder flushes first,
+ *   table_builder_bacs.cpp:186-189); size >= 16; key_size = Fixed32(p) >= 8 and
+ *   8 + key_size + Fixed32(p + 4) == size (the assert of table.cc:501; the
+ *   reference reads garbage in release builds); the pair's type byte
+ *   p[8 + key_size - 8] is 0 or 1; the pair's user key equals the Get's (the
+ *   reference would leave kNotFound and search on -- only a table whose index
+ *   and data disagree gets here);
+ *   type 0: DLSM_GET_DELETED, length 0; type 1: DLSM_GET_FOUND, the value the
+ *   value_size bytes at p + 8 + key_size.
+ * Outputs, a pure function of the inputs:
+ *   value_off_dev[i], i <= m: the exclusive sum of the value lengths of the
+ *   items below i, exact whatever values_cap is; value_off_dev[m] is the total;
+ *   entries past m are not touched;
+ *   values_dev (16-byte aligned): every byte p < min(total, values_cap) holds
+ *   the value byte that belongs there; nothing at or past values_cap and
+ *   nothing past the total is written;
+ *   n_corrupt_dev (or NULL): the items this call set to DLSM_GET_CORRUPT.
+ * cap == 0 returns DLSM_OK and touches nothing; cap <= UINT32_MAX.
+ * DLSM_OPT_FAULT_INJECT makes the calls return the injected error.
+ * Asynchronous on the context's stream: three launches whatever m is, no host
+ * read-back.  dlsm_kv_read is the host-memory form (every array on the host,
+ * count a host value or NULL, values of any alignment).  Synchronous; state is
+ * replaced only when the call succeeds. */
+typedef struct {
+  const uint8_t* base;
+  uint64_t len;
+} dlsm_data_chunk;
+typedef struct dlsm_tabledata dlsm_tabledata;
+
+int dlsm_tabledata_create(dlsm_ctx* ctx, const dlsm_data_chunk* chunks, const uint32_t* chunk_begin, int n_files,
+                          int chunks_are_device, dlsm_tabledata** out);
+int dlsm_tabledata_destroy(dlsm_tabledata* td);
+int dlsm_tabledata_size(const dlsm_tabledata* td, int* n_files, uint64_t* n_chunks, uint64_t* device_bytes);
+
+int dlsm_kv_read_dev(dlsm_ctx* ctx, const dlsm_tabledata* td, const dlsm_keyset* keys, const uint32_t* gets_dev,
+                     const uint64_t* count_dev, uint64_t cap, uint8_t* state_dev, const dlsm_kv_handle* handle_dev,
+                     uint64_t* value_off_dev, uint8_t* values_dev, uint64_t values_cap, uint64_t* n_corrupt_dev);
+int dlsm_kv_read(dlsm_ctx* ctx, const dlsm_tabledata* td, const dlsm_keyset* keys, const uint32_t* gets,
+                 const uint64_t* count, uint64_t cap, uint8_t* state, const dlsm_kv_handle* handle,
+                 uint64_t* value_off, uint8_t* values, uint64_t values_cap, uint64_t* n_corrupt);
+/* Host only (no device touched): the rules above for one Get on one file's
+ * chunks (host memory; handle->file is not looked at) -- the per-Get path.
+ * *state is read and updated; *value points into the chunk. */
+int dlsm_kv_pair_read(const dlsm_data_chunk* chunks, uint32_t n_chunks, const dlsm_kv_handle* handle,
+                      const uint8_t* user_key, uint64_t key_len, uint8_t* state, const uint8_t** value,
+                      uint32_t* value_len);
+/* Items per workgroup chunk of the size pass and output bytes per workgroup
+ * step of the copy (the sizes around which the tests are built). */
+uint32_t dlsm_kv_read_chunk(void);
+uint32_t dlsm_kv_read_span(void);
+/* The last dlsm_kv_read_dev of the context, once its work has completed (after
+ * dlsm_ctx_sync): launch_ms[3] (or NULL) gets the device time of the size,
+ * offset and copy launches from events recorded around them (zeros where no
+ * call has run); *copy_wgs (or NULL) the copy's persistent grid, two
+ * workgroups per compute unit of the context's device (0 before the first
+ * call). */
+int dlsm_kv_read_stats(const dlsm_ctx* ctx, double* launch_ms, uint32_t* copy_wgs);
 
 /* ---- legacy FilterPolicy format (util/bloom.cc) ------------------------- */
 

@@ -1681,4 +1681,134 @@ class TableIndex {
   int last_status_ = DLSM_OK;
 };
 
+namespace host {
+
+// dlsm_kv_read's arrays from a host loop over the items: the rules are the
+// library's (dlsm_kv_pair_read); files[f] empty: no data held for f.
+inline int ReadBatch(const std::vector<std::vector<dlsm_data_chunk>>& files, const dlsm_keyset& keys,
+                     const uint32_t* gets, const uint64_t* count, uint64_t cap, uint8_t* state,
+                     const dlsm_kv_handle* handle, uint64_t* value_off, uint8_t* values, uint64_t values_cap,
+                     uint64_t* n_corrupt) {
+  if (keys.n > 0xffffffffull || (keys.n && !keys.bytes) || cap > 0xffffffffull) return DLSM_E_ARG;
+  const uint64_t m = count ? (*count < cap ? *count : cap) : cap;
+  if (cap && (!value_off || (m && (!state || !handle)) || (values_cap && !values))) return DLSM_E_ARG;
+  if (cap == 0) return DLSM_OK;
+  uint64_t at = 0, bad = 0;
+  for (uint64_t i = 0; i < m; i++) {
+    value_off[i] = at;
+    if (state[i] != DLSM_GET_FOUND) continue;
+    const uint64_t g = gets ? gets[i] : i;
+    const dlsm_kv_handle& h = handle[i];
+    uint8_t st = DLSM_GET_CORRUPT;
+    const uint8_t* v = nullptr;
+    uint32_t vl = 0;
+    if (g < keys.n && h.file < files.size() && !files[h.file].empty()) {
+      const uint64_t ko = keys.offsets ? keys.offsets[g] : g * keys.key_len;
+      uint64_t len = keys.offsets ? keys.offsets[g + 1] - ko : keys.key_len;
+      len = len > keys.suffix_len ? len - keys.suffix_len : 0;  // ExtractUserKey
+      st = DLSM_GET_FOUND;
+      if (dlsm_kv_pair_read(files[h.file].data(), static_cast<uint32_t>(files[h.file].size()), &h, keys.bytes + ko, len,
+                            &st, &v, &vl) != DLSM_OK)
+        st = DLSM_GET_CORRUPT;
+    }
+    state[i] = st;
+    bad += st == DLSM_GET_CORRUPT;
+    if (st != DLSM_GET_FOUND) continue;
+    if (at < values_cap && vl) memcpy(values + at, v, static_cast<size_t>(vl < values_cap - at ? vl : values_cap - at));
+    at += vl;
+  }
+  value_off[m] = at;
+  if (n_corrupt) *n_corrupt = bad;
+  return DLSM_OK;
+}
+
+}  // namespace host
+
+// The data regions of a version's tables (the chunks remote_data_mrs names):
+// FromChunks keeps a copy of every chunk.  ReadPair (one Get, the per-Get
+// path: ReadKVPair, the two lengths, SaveValue, value->assign) is answered on
+// the host; ReadBatch (a seeked batch in host memory) runs on the GPU and, if
+// the device cannot take it, in host::ReadBatch with identical arrays
+// (counted: dlsm_fallback_note).  A file given without chunks holds no data.
+class TableData {
+ public:
+  static TableData* FromChunks(const std::vector<std::vector<Slice>>& files, dlsm_ctx* ctx = nullptr) {
+    TableData* td = new TableData(ctx);
+    td->bytes_.resize(files.size());
+    td->chunks_.resize(files.size());
+    for (size_t f = 0; f < files.size(); f++) {
+      for (const Slice& c : files[f]) td->bytes_[f].push_back(std::string(c.data() ? c.data() : "", c.size()));
+      for (const std::string& s : td->bytes_[f])  // (the strings no longer move)
+        td->chunks_[f].push_back(dlsm_data_chunk{reinterpret_cast<const uint8_t*>(s.data()), s.size()});
+    }
+    return td;
+  }
+  ~TableData() {
+    if (dev_) dlsm_tabledata_destroy(dev_);
+  }
+  TableData(const TableData&) = delete;
+  TableData& operator=(const TableData&) = delete;
+
+  int n_files() const { return static_cast<int>(chunks_.size()); }
+  // The value read of one Get: *state is the seek's (read and updated); *value
+  // is assigned only where the state stays DLSM_GET_FOUND.
+  int ReadPair(const dlsm_kv_handle& handle, const Slice& user_key, std::string* value, uint8_t* state) const {
+    if (!state) return DLSM_E_ARG;
+    if (*state != DLSM_GET_FOUND) return DLSM_OK;
+    if (handle.file >= chunks_.size() || chunks_[handle.file].empty()) {
+      *state = DLSM_GET_CORRUPT;
+      return DLSM_OK;
+    }
+    const uint8_t* v = nullptr;
+    uint32_t vl = 0;
+    const int st = dlsm_kv_pair_read(chunks_[handle.file].data(), static_cast<uint32_t>(chunks_[handle.file].size()),
+                                     &handle, reinterpret_cast<const uint8_t*>(user_key.data()), user_key.size(), state,
+                                     &v, &vl);
+    if (st == DLSM_OK && *state == DLSM_GET_FOUND && value) value->assign(reinterpret_cast<const char*>(v), vl);
+    return st;
+  }
+  // dlsm_kv_read on host arrays (see dlsm_kv_read_dev for the outputs).
+  int ReadBatch(const dlsm_keyset& keys, const uint32_t* gets, const uint64_t* count, uint64_t cap, uint8_t* state,
+                const dlsm_kv_handle* handle, uint64_t* value_off, uint8_t* values, uint64_t values_cap,
+                uint64_t* n_corrupt) {
+    dlsm_ctx* ctx = ctx_ ? ctx_ : ThreadContext();
+    last_status_ = ctx ? device_read(ctx, keys, gets, count, cap, state, handle, value_off, values, values_cap, n_corrupt)
+                       : DLSM_E_DEVICE;
+    if (last_status_ == DLSM_OK || last_status_ == DLSM_E_ARG) return last_status_;  // bad arguments stay bad
+    const int st = host::ReadBatch(chunks_, keys, gets, count, cap, state, handle, value_off, values, values_cap, n_corrupt);
+    if (st == DLSM_OK) dlsm_fallback_note(ctx);
+    return st;
+  }
+  // The last ReadBatch's GPU status (the arrays are complete either way).
+  int status() const { return last_status_; }
+
+ private:
+  explicit TableData(dlsm_ctx* ctx) : ctx_(ctx) {}
+  int device_read(dlsm_ctx* ctx, const dlsm_keyset& keys, const uint32_t* gets, const uint64_t* count, uint64_t cap,
+                  uint8_t* state, const dlsm_kv_handle* handle, uint64_t* value_off, uint8_t* values, uint64_t values_cap,
+                  uint64_t* n_corrupt) {
+    if (!dev_ || dev_device_ != dlsm_ctx_device(ctx)) {
+      if (dev_) dlsm_tabledata_destroy(dev_);
+      dev_ = nullptr;
+      std::vector<dlsm_data_chunk> flat;
+      std::vector<uint32_t> begin(1, 0);
+      for (const auto& f : chunks_) {
+        flat.insert(flat.end(), f.begin(), f.end());
+        begin.push_back(static_cast<uint32_t>(flat.size()));
+      }
+      const int st = dlsm_tabledata_create(ctx, flat.data(), begin.data(), n_files(), 0, &dev_);
+      if (st != DLSM_OK) return st == DLSM_E_ARG ? DLSM_E_DEVICE : st;  // (the chunks are the adapter's own)
+      dev_device_ = dlsm_ctx_device(ctx);
+    }
+    // dlsm_kv_read replaces the states only after its last device operation has completed
+    return dlsm_kv_read(ctx, dev_, &keys, gets, count, cap, state, handle, value_off, values, values_cap, n_corrupt);
+  }
+  std::vector<std::vector<std::string>> bytes_;          // the chunks as given
+  std::vector<std::vector<dlsm_data_chunk>> chunks_;
+  dlsm_ctx* ctx_;
+  dlsm_tabledata* dev_ = nullptr;
+  int dev_device_ = -1;
+  int last_status_ = DLSM_OK;
+};
+
 }  // namespace dlsm_adapter
