@@ -34,6 +34,7 @@ __all__ = [
     "TableIndex", "BLOCK_INDEX", "GET_NOTFOUND", "GET_FOUND", "GET_DELETED", "GET_CORRUPT", "KV_HANDLE",
     "index_fence_interval", "index_seek_block", "index_block_check", "index_block_seek",
     "TableData", "kv_read_chunk", "kv_read_span", "kv_pair_read",
+    "table_build", "table_build_chunk", "table_build_span", "table_build_bound",
 ]
 
 PATH_AUTO, PATH_DIRECT, PATH_SLICED = 0, 1, 2
@@ -115,6 +116,70 @@ def kv_read_chunk() -> int:
 def kv_read_span() -> int:
     """Output bytes per workgroup step of the value read's copy."""
     return int(lib().dlsm_kv_read_span())
+
+
+TABLE_DATA_CAP, TABLE_INDEX_CAP, TABLE_CHUNK_CAP, TABLE_SHORT_KEY = 1, 2, 4, 8
+TABLE_PAIR_TOO_BIG, TABLE_INDEX_TOO_BIG, TABLE_OVERSIZE_PAIR = 16, 32, 64
+
+
+def table_build_chunk() -> int:
+    """Pairs per workgroup chunk of the table build's size and offset passes."""
+    return int(lib().dlsm_table_build_chunk())
+
+
+def table_build_span() -> int:
+    """Output bytes per workgroup step of the table build's region write."""
+    return int(lib().dlsm_table_build_span())
+
+
+def table_build_bound(n: int, key_bytes: int, value_bytes: int):
+    """(the region's exact length, an index capacity no block of the pairs passes)."""
+    d, x = C.c_uint64(), C.c_uint64()
+    check(lib().dlsm_table_build_bound(n, key_bytes, value_bytes, C.byref(d), C.byref(x)), "table_build_bound")
+    return int(d.value), int(x.value)
+
+
+def _table_io(keys: "Keys", values, value_off, value_len: int, chunk_bytes: int, data, data_cap, index, index_cap,
+              chunk_end, chunk_cap, built):
+    n = keys.n
+    if value_off is not None:
+        _need(value_off, 8 * (n + 1), "value_off")
+    else:
+        _need(values, n * value_len, "values")
+    data_cap = _nbytes(data) if data_cap is None else int(data_cap)
+    index_cap = _nbytes(index) if index_cap is None else int(index_cap)
+    chunk_cap = _nbytes(chunk_end) // 8 if chunk_cap is None else int(chunk_cap)
+    for x, nb, what in ((data, data_cap, "data"), (index, index_cap, "index"), (chunk_end, 8 * chunk_cap, "chunk_end"),
+                        (built, 32, "built")):
+        _need(x, nb, what)
+    ti = _L.dlsm_table_input(keys.c(), _ptr(values), _ptr(value_off), value_len, chunk_bytes)
+    to = _L.dlsm_table_output(_ptr(data), data_cap, _ptr(index), index_cap, _ptr(chunk_end), chunk_cap, _ptr(built))
+    return ti, to
+
+
+def table_build(keys: "Keys", values: np.ndarray, *, value_off: Optional[np.ndarray] = None, value_len: int = 0,
+                chunk_bytes: int = 0, data_cap: Optional[int] = None, index_cap: Optional[int] = None,
+                chunk_cap: Optional[int] = None, ctx: Optional["Context"] = None):
+    """The host form of the table build (dlsm_table_build; no device is
+    touched): ``keys`` are the internal keys in table order (host arrays),
+    ``values`` the packed values with ``value_off`` (uint64[n + 1]) or one
+    ``value_len``.  Returns (data uint8, index uint8, chunk_end uint64, built)
+    with built = (data_bytes, index_bytes, n_chunks, flags); the arrays are cut
+    at min(total, cap).  The caps default to what the pairs need."""
+    n = keys.n
+    kb = int(keys.offsets[n] - keys.offsets[0]) if keys.offsets is not None else n * keys.key_len
+    vb = int(value_off[n] - value_off[0]) if value_off is not None else n * value_len
+    need_d, need_i = table_build_bound(n, kb, vb)
+    data_cap = need_d if data_cap is None else int(data_cap)
+    index_cap = need_i if index_cap is None else int(index_cap)
+    chunk_cap = n + 1 if chunk_cap is None else int(chunk_cap)
+    data, index = np.zeros(max(data_cap, 1), dtype=np.uint8), np.zeros(max(index_cap, 1), dtype=np.uint8)
+    ends, built = np.zeros(max(chunk_cap, 1), dtype=np.uint64), np.zeros(4, dtype=np.uint64)
+    ti, to = _table_io(keys, values, value_off, value_len, chunk_bytes, data, data_cap, index, index_cap, ends,
+                       chunk_cap, built)
+    check(lib().dlsm_table_build(ctx.h if ctx is not None else None, C.byref(ti), C.byref(to)), "table_build")
+    b = tuple(int(x) for x in built)
+    return data[:min(b[0], data_cap)], index[:min(b[1], index_cap)], ends[:min(b[2], chunk_cap)], b
 
 
 def kv_pair_read(chunks, handle, user_key: bytes, state: int = GET_FOUND):
@@ -961,6 +1026,31 @@ class Context:
         check(lib().dlsm_kv_read(self.h, td.h, C.byref(ks), _ptr(gets), _ptr(cnt), cap, _ptr(state), _ptr(handle),
                                  _ptr(value_off), _ptr(values), values_cap, _ptr(bad)), "kv_read")
         return value_off[:m + 1], values[:min(int(value_off[m]), values_cap)], int(bad[0])
+
+    # -- table build: the data region and the sealed index block ----------------
+    def table_build_dev(self, keys: Keys, values, data, index, chunk_end, built, *, value_off=None, value_len: int = 0,
+                        chunk_bytes: int = 0, data_cap: Optional[int] = None, index_cap: Optional[int] = None,
+                        chunk_cap: Optional[int] = None):
+        """Build a table's data region and sealed index block on the device:
+        ``keys`` are the internal keys in table order, ``values`` the packed
+        values with ``value_off`` (device uint64[n + 1]) or one ``value_len``.
+        data / index (device uint8, 16-byte aligned), chunk_end (device uint64)
+        and built (device uint64[4]: data_bytes, index_bytes, n_chunks, flags)
+        are written; the caps default to the buffers' lengths.  Asynchronous."""
+        ti, to = _table_io(keys, values, value_off, value_len, chunk_bytes, data, data_cap, index, index_cap,
+                           chunk_end, chunk_cap, built)
+        check(lib().dlsm_table_build_dev(self.h, C.byref(ti), C.byref(to)), "table_build_dev")
+
+    def table_build(self, keys: Keys, values, **kw):
+        """The host-memory form (see dlsm_amd.table_build)."""
+        return table_build(keys, values, ctx=self, **kw)
+
+    def table_build_stats(self):
+        """(size, offsets, region, index, seal) device milliseconds of the last
+        table_build_dev (call after sync) and the writes' grid in workgroups."""
+        ms, wgs = (C.c_double * 5)(), C.c_uint32()
+        check(lib().dlsm_table_build_stats(self.h, ms, C.byref(wgs)), "table_build_stats")
+        return tuple(float(x) for x in ms), int(wgs.value)
 
     # -- full filter probe --------------------------------------------------
     def filterset(self, filters, on_device: bool = False, *, sealed: bool = False,

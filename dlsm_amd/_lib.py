@@ -57,6 +57,21 @@ class dlsm_data_chunk(C.Structure):
     _fields_ = [("base", C.c_void_p), ("len", C.c_uint64)]
 
 
+class dlsm_table_input(C.Structure):
+    _fields_ = [("keys", dlsm_keyset), ("values", C.c_void_p), ("value_off", C.c_void_p), ("value_len", C.c_uint32),
+                ("chunk_bytes", C.c_uint64)]
+
+
+class dlsm_table_built(C.Structure):
+    _fields_ = [("data_bytes", C.c_uint64), ("index_bytes", C.c_uint64), ("n_chunks", C.c_uint64),
+                ("flags", C.c_uint64)]
+
+
+class dlsm_table_output(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("data_cap", C.c_uint64), ("index", C.c_void_p), ("index_cap", C.c_uint64),
+                ("chunk_end", C.c_void_p), ("chunk_cap", C.c_uint64), ("built", C.c_void_p)]
+
+
 class DlsmError(RuntimeError):
     def __init__(self, status: int, what: str = ""):
         self.status = status
@@ -188,6 +203,12 @@ SIGNATURES = [
     ("dlsm_kv_read_chunk", C.c_uint32, []),
     ("dlsm_kv_read_span", C.c_uint32, []),
     ("dlsm_kv_read_stats", C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
+    ("dlsm_table_build_dev", C.c_int, [_VP, C.POINTER(dlsm_table_input), C.POINTER(dlsm_table_output)]),
+    ("dlsm_table_build", C.c_int, [_VP, C.POINTER(dlsm_table_input), C.POINTER(dlsm_table_output)]),
+    ("dlsm_table_build_bound", C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, _U64P, _U64P]),
+    ("dlsm_table_build_chunk", C.c_uint32, []),
+    ("dlsm_table_build_span", C.c_uint32, []),
+    ("dlsm_table_build_stats", C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
     ("dlsm_bloom_full_probe", C.c_int, [_VP, _VP, C.POINTER(dlsm_keyset), _VP]),
     ("dlsm_bloom_full_probe_hashed_dev", C.c_int, [_VP, _VP, C.POINTER(dlsm_keyset), _VP]),
     ("dlsm_bloom_hash_batch", C.c_int, [C.POINTER(dlsm_keyset), _VP, C.c_int]),

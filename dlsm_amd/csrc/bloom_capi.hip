@@ -160,6 +160,12 @@ struct dlsm_ctx {
   DevBuf<uint8_t> kv_ws;     // value read: lengths, source addresses, partial sums (plan::KvReadPlan's layout)
   hipEvent_t ev_kv[4] = {};  // value read: around its three launches (dlsm_kv_read_stats)
   bool kv_timed = false;     // the last dlsm_kv_read_dev recorded all four
+  DevBuf<uint8_t> tb_ws;     // table build: offsets, entry starts, partial sums (plan::TableBuildPlan's layout)
+  hipEvent_t ev_tb[6] = {};  // table build: around its four launches and the seal (dlsm_table_build_stats)
+  bool tb_timed = false;     // the last dlsm_table_build_dev recorded all six
+  const uint8_t* tb_seal_index = nullptr;  // table build: the block whose seal descriptor lies in tb_ws ...
+  uint64_t tb_seal_cap = 0, tb_seal_gen = 0;  // ... its capacity, and tb_ws's generation then
+  hipStream_t tb_seal_stream = nullptr;       // ... and the stream the descriptor went up on
   int cus = 0;               // the device's compute units (0: not asked yet)
   // host-API staging
   DevBuf<uint8_t> st_keys;
@@ -589,6 +595,7 @@ int dlsm_ctx_destroy(dlsm_ctx* ctx) {
   ctx->plan_ws.release();
   ctx->route_ws.release();
   ctx->kv_ws.release();
+  ctx->tb_ws.release();
   ctx->sel.release();
   ctx->st_keys.release();
   ctx->st_offs.release();
@@ -606,6 +613,8 @@ int dlsm_ctx_destroy(dlsm_ctx* ctx) {
   ctx->ing_partial.release();
   ctx->ing_rec.release();
   for (hipEvent_t e : ctx->ev_kv)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : ctx->ev_tb)
     if (e) (void)hipEventDestroy(e);
   if (ctx->ev_ing0) (void)hipEventDestroy(ctx->ev_ing0);
   if (ctx->ev_ing1) (void)hipEventDestroy(ctx->ev_ing1);
@@ -816,7 +825,7 @@ int dlsm_ctx_stats(dlsm_ctx* ctx, uint64_t* device_allocs, uint64_t* device_byte
   add(ctx->vgl); add(ctx->vabyte); add(ctx->vplan); add(ctx->plan_ws); add(ctx->route_ws);
   add(ctx->st_keys); add(ctx->st_offs); add(ctx->st_out); add(ctx->st_len); add(ctx->st_filter);
   add(ctx->crc_streams); add(ctx->crc_partial); add(ctx->crc_tabs); add(ctx->crc_outp); add(ctx->crc_cap);
-  add(ctx->crc_val); add(ctx->sel); add(ctx->kv_ws);
+  add(ctx->crc_val); add(ctx->sel); add(ctx->kv_ws); add(ctx->tb_ws);
   if (device_allocs) *device_allocs = n;
   if (device_bytes) *device_bytes = b;
   return DLSM_OK;
@@ -3038,6 +3047,214 @@ int dlsm_kv_read(dlsm_ctx* ctx, const dlsm_tabledata* td, const dlsm_keyset* key
   if (m) DLSM_TRY(hipMemcpyAsync(new_state.data(), st + so, m, hipMemcpyDeviceToHost, s));
   if (nb || m) DLSM_TRY(ctx_sync(ctx, s));
   if (m) memcpy(state, new_state.data(), m);
+  return DLSM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Table build: the data region and the sealed index block of a run of pairs
+// (TableBuilder_BACS::Add, table_builder_bacs.cpp:186-226; table_build.hip)
+// ---------------------------------------------------------------------------
+uint32_t dlsm_table_build_chunk(void) { return kTbChunk; }
+uint32_t dlsm_table_build_span(void) { return kTbSpan; }
+
+int dlsm_table_build_bound(uint64_t n, uint64_t key_bytes, uint64_t value_bytes, uint64_t* data_bytes,
+                           uint64_t* index_cap) {
+  return plan_table_build_bound(n, key_bytes, value_bytes, data_bytes, index_cap);
+}
+
+static int table_build_args(const dlsm_table_input* in, const dlsm_table_output* out) {
+  if (!in || !out || !out->built || in->keys.n > 0xffffffffull) return DLSM_E_ARG;
+  DLSM_CHECK(validate_keyset(in->keys));
+  if ((out->data_cap && !out->data) || (out->index_cap && !out->index) || (out->chunk_cap && !out->chunk_end))
+    return DLSM_E_ARG;
+  if (in->keys.n && !in->values && (in->value_off || in->value_len)) return DLSM_E_ARG;
+  return DLSM_OK;
+}
+
+static TbSource table_build_source(const dlsm_table_input& in, const uint64_t* off) {
+  TbSource s{};
+  s.kbytes = in.keys.bytes;
+  s.koff = in.keys.offsets;
+  s.klen = in.keys.key_len;
+  s.vbytes = in.values;
+  s.voff = in.value_off;
+  s.vlen = in.value_len;
+  s.off = off;
+  return s;
+}
+
+int dlsm_table_build_dev(dlsm_ctx* ctx, const dlsm_table_input* in, const dlsm_table_output* out) {
+  if (!ctx) return DLSM_E_ARG;
+  DLSM_CHECK(table_build_args(in, out));
+  if (!aligned(out->data, 16) || !aligned(out->index, 16) || !aligned(out->chunk_end, 8) || !aligned(out->built, 8) ||
+      !aligned(in->keys.offsets, 8) || !aligned(in->value_off, 8))
+    return DLSM_E_ARG;
+  TableBuildPlan P;
+  DLSM_CHECK(plan_table_build(in->keys.n, kSortMaxWgs, P));
+  if (ctx->fault) return -ctx->fault;
+  DeviceGuard g(ctx->device);
+  if (!ctx->cus) {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || cus <= 0)
+      cus = kTbWgs / kTbWgsPerCu;
+    ctx->cus = cus;
+  }
+  const uint32_t wgs = plan_table_build_wgs(static_cast<uint32_t>(ctx->cus));
+  for (hipEvent_t& e : ctx->ev_tb)
+    if (!e) DLSM_TRY(hipEventCreate(&e));
+  ctx->tb_timed = false;
+  DLSM_CHECK(ctx->tb_ws.ensure(P.bytes));
+  uint8_t* ws = ctx->tb_ws.p;
+  TbDev a{};
+  a.off = reinterpret_cast<uint64_t*>(ws + P.off_off);
+  a.src = table_build_source(*in, a.off);
+  a.n = in->keys.n;
+  a.chunk_bytes = in->chunk_bytes;
+  a.data = out->data;
+  a.data_cap = out->data_cap;
+  a.index = out->index;
+  a.index_cap = out->index_cap;
+  a.chunk_end = out->chunk_end;
+  a.chunk_cap = out->chunk_cap;
+  a.built = reinterpret_cast<uint64_t*>(out->built);
+  a.erel = reinterpret_cast<uint64_t*>(ws + P.erel_off);
+  a.es = reinterpret_cast<uint32_t*>(ws + P.es_off);
+  a.wg_sum = reinterpret_cast<uint64_t*>(ws + P.sum_off);
+  a.wg_esum = reinterpret_cast<uint64_t*>(ws + P.esum_off);
+  a.wg_flags = reinterpret_cast<uint64_t*>(ws + P.flag_off);
+  a.tot = reinterpret_cast<uint64_t*>(ws + P.tot_off);
+  a.cpw = P.cpw;
+  a.nwg = P.nwg;
+  a.copy_wgs = wgs;
+  DLSM_TRY(launch_table_build(a, wgs, ctx->ev_tb, ctx->stream));
+  // the seal: crc32c over contents || type with the device-side length tot[1]
+  // (0: the block does not fit or the input is malformed -- nothing is sealed),
+  // the trailer written in place; tot[2] takes the sealed length
+  // Its descriptor [stream | out | cap] lies in the workspace: one 64-byte
+  // upload, and none when the call seals the block the last one sealed.
+  uint8_t* seal = ws + P.seal_off;
+  if (crc_stream_size() > 48) return DLSM_E_ARG;
+  if (ctx->tb_seal_index != out->index || ctx->tb_seal_cap != out->index_cap || ctx->tb_seal_gen != ctx->tb_ws.gen ||
+      ctx->tb_seal_stream != ctx->stream) {  // (the copy is ordered on the stream it went up on)
+    alignas(8) uint8_t d[64] = {};
+    crc_stream_fill(d, out->index, a.tot + 1, 0, 1);
+    memcpy(d + 48, &out->index, 8);
+    memcpy(d + 56, &out->index_cap, 8);
+    DLSM_CHECK(ctx_upload(ctx, seal, d, sizeof(d), ctx->stream));
+    ctx->tb_seal_index = out->index;
+    ctx->tb_seal_cap = out->index_cap;
+    ctx->tb_seal_gen = ctx->tb_ws.gen;
+    ctx->tb_seal_stream = ctx->stream;
+  }
+  const int max_parts =
+      static_cast<int>(std::max<uint64_t>(1, crc_max_parts(std::min<uint64_t>(out->index_cap, (uint64_t(1) << 32) + 5))));
+  DLSM_CHECK(ctx->crc_partial.ensure(max_parts));
+  DLSM_TRY(launch_crc_streams(seal, 1, max_parts, ctx->crc_partial.p, reinterpret_cast<uint8_t* const*>(seal + 48),
+                              reinterpret_cast<const uint64_t*>(seal + 56), a.tot + 2, nullptr, ctx->stream));
+  DLSM_TRY(hipEventRecord(ctx->ev_tb[5], ctx->stream));
+  ctx->tb_timed = true;
+  return DLSM_OK;
+}
+
+int dlsm_table_build_stats(const dlsm_ctx* ctx, double* launch_ms, uint32_t* write_wgs) {
+  if (!ctx) return DLSM_E_ARG;
+  if (write_wgs) *write_wgs = ctx->cus ? plan_table_build_wgs(static_cast<uint32_t>(ctx->cus)) : 0;
+  if (launch_ms) {
+    for (int j = 0; j < 5; j++) launch_ms[j] = 0;
+    if (!ctx->tb_timed) return DLSM_OK;
+    DeviceGuard g(ctx->device);
+    for (int j = 0; j < 5; j++) {
+      float ms = 0;
+      DLSM_TRY(hipEventElapsedTime(&ms, ctx->ev_tb[j], ctx->ev_tb[j + 1]));
+      launch_ms[j] = ms;
+    }
+  }
+  return DLSM_OK;
+}
+
+// The host form: the passes of table_build.hip one after the other on the
+// host, through the same functions of table_build.h.
+int dlsm_table_build(dlsm_ctx* ctx, const dlsm_table_input* in, const dlsm_table_output* out) {
+  DLSM_CHECK(table_build_args(in, out));
+  if (ctx && ctx->fault) return -ctx->fault;
+  const uint64_t n = in->keys.n;
+  std::vector<uint64_t> off(n + 1);
+  std::vector<uint32_t> es(n + 2);
+  const TbSource src = table_build_source(*in, off.data());
+  uint64_t flags = 0, total = 0, E = 0;
+  for (uint64_t i = 0; i < n; i++) {
+    const uint64_t ks = src.key_size(i), vs = src.value_size(i), p = tb_pair_size(ks, vs);
+    if (ks < 8) flags |= kTbShortKey;
+    if (ks > 0xffffffffull || vs > 0xffffffffull || p > 0xffffffffull) flags |= kTbPairTooBig;
+    off[i] = total;
+    es[i] = static_cast<uint32_t>(E);
+    E += tb_entry_len(ks, total, p);
+    total += p;
+  }
+  off[n] = total;
+  es[n] = static_cast<uint32_t>(n);
+  es[n + 1] = 0;
+  const uint64_t ctot = E + 4 * n + 4;
+  if (total > out->data_cap) flags |= kTbDataCap;
+  if (ctot > 0xffffffffull) flags |= kTbIndexTooBig;
+  if (ctot + 5 > out->index_cap) flags |= kTbIndexCap;
+  const bool bad = (flags & kTbMalformed) != 0;
+  uint64_t nch = 0;
+  if (bad) {
+    // only `built` is specified: the chain is not walked, no chunk is counted
+  } else if (n == 0 || in->chunk_bytes == 0) {
+    if (out->chunk_cap) out->chunk_end[0] = total;
+    nch = 1;
+  } else {
+    for (uint64_t at = 0; at < n; nch++) {
+      bool oversize;
+      const uint64_t next = tb_chunk_next(off.data(), n, at, in->chunk_bytes, &oversize);
+      if (oversize) flags |= kTbOversizePair;
+      if (nch < out->chunk_cap) out->chunk_end[nch] = off[next];
+      at = next;
+    }
+  }
+  if (nch > out->chunk_cap) flags |= kTbChunkCap;
+  *out->built = dlsm_table_built{total, ctot + 5, nch, flags};
+  if (bad) return DLSM_OK;
+  // the region: the same unit over the bytes below the cap (host memory has no
+  // alignment rule: a unit is assembled in a 16-byte slot of its own)
+  const uint64_t dlimit = std::min(total, out->data_cap);
+  alignas(16) uint8_t slot[16];
+  for (uint64_t u = 0; u < dlimit; u += 16) {
+    const uint64_t p1 = std::min(u + 16, dlimit);
+    tb_region_unit(src, n, u, p1, slot);
+    memcpy(out->data + u, slot, p1 - u);
+  }
+  // the index contents span by span: the entries into a tile, then the units
+  const uint64_t ilimit = std::min(ctot, out->index_cap);
+  std::vector<uint8_t> tile(kTbIndexSpan);
+  uint64_t first = 0;
+  for (uint64_t q0 = 0; q0 < ilimit; q0 += kTbIndexSpan) {
+    const uint64_t q1 = std::min<uint64_t>(q0 + kTbIndexSpan, ilimit);
+    if (q0 < E) {
+      const uint64_t qe = std::min(q1, E);
+      const int64_t len = static_cast<int64_t>(qe - q0);
+      while (first + 1 < n && es[first + 1] <= q0) first++;
+      for (uint64_t i = first; i < n && es[i] < qe; i++) {
+        const uint64_t ks = src.key_size(i), size = off[i + 1] - off[i];
+        const int64_t at = static_cast<int64_t>(es[i]) - static_cast<int64_t>(q0), k0 = at + tb_entry_head(ks);
+        tb_entry_write(tile.data(), len, at, ks, off[i], size);
+        const int64_t b0 = std::max<int64_t>(0, -k0), b1 = std::min<int64_t>(static_cast<int64_t>(ks), len - k0);
+        if (b1 > b0) memcpy(tile.data() + k0 + b0, reinterpret_cast<const uint8_t*>(src.key_src(i)) + b0, b1 - b0);
+      }
+    }
+    for (uint64_t q = q0; q < q1; q += 16) {
+      const uint64_t e1 = std::min(q + 16, ilimit);
+      tb_index_unit(tile.data(), q0, es.data(), E, ctot, q, ilimit, slot);
+      memcpy(out->index + q, slot, e1 - q);
+    }
+  }
+  if (ctot + 5 <= out->index_cap) {
+    out->index[ctot] = 0;  // kNoCompression
+    const uint32_t m = dlsm_crc32c_mask(dlsm_crc32c_extend(0, out->index, ctot + 1));
+    memcpy(out->index + ctot + 1, &m, 4);
+  }
   return DLSM_OK;
 }
 

@@ -10,6 +10,7 @@
 #include "kv_read.h"
 #include "read_plan.h"
 #include "shard_route.h"
+#include "table_build.h"
 
 namespace dlsm {
 
@@ -519,5 +520,31 @@ struct KvReadDev {
 };
 // ev: four events recorded around the three launches, or nullptr.
 hipError_t launch_kv_read(const KvReadDev& a, uint32_t copy_wgs, hipEvent_t* ev, hipStream_t s);
+
+// table_build.hip: the data region and index block of a table from its pairs
+// (dlsm_table_build_dev).  Workspace in plan::TableBuildPlan's layout.
+struct TbDev {
+  TbSource src;        // the inputs; src.off = off
+  uint64_t n;
+  uint64_t chunk_bytes;
+  uint8_t* data;       // 16-byte aligned
+  uint64_t data_cap;
+  uint8_t* index;      // 16-byte aligned
+  uint64_t index_cap;
+  uint64_t* chunk_end;
+  uint64_t chunk_cap;
+  uint64_t* built;     // dlsm_table_built: data_bytes, index_bytes, n_chunks, flags
+  uint64_t* off;       // workspace u64[n + 1]: the pairs' offsets and the total
+  uint64_t* erel;      // workspace u64[n]: entry starts relative to the offsets pass's workgroup
+  uint32_t* es;        // workspace u32[n + 2]: entry starts (the restart array), n, a pad
+  uint64_t* wg_sum;    // workspace u64[nwg]: pair bytes per workgroup
+  uint64_t* wg_esum;   // workspace u64[nwg]: entry bytes per workgroup
+  uint64_t* wg_flags;  // workspace u64[nwg]: malformed-input bits per workgroup
+  uint64_t* tot;       // workspace u64[4]: entry bytes, the seal's length, its result, the bits after the offsets pass
+  uint32_t cpw, nwg;   // plan::sort_grid(n, kTbChunk, kSortMaxWgs), at least one workgroup
+  uint32_t copy_wgs;   // the region write's persistent grid
+};
+// ev: five events recorded around the four launches, or nullptr.
+hipError_t launch_table_build(const TbDev& a, uint32_t index_wgs, hipEvent_t* ev, hipStream_t s);
 
 }  // namespace dlsm

@@ -1024,5 +1024,56 @@ inline int plan_tabledata(const dlsm_data_chunk* chunks, const uint32_t* chunk_b
   return DLSM_OK;
 }
 
+// ---- table build (table_build.hip) ---------------------------------------------
+// dlsm_table_build_dev from the pair count alone: the size and offset passes on
+// sort_grid's grid of kTbChunk pairs (one workgroup where there is no pair: it
+// writes the totals), the writes' persistent grids, and the workspace layout
+// (byte offsets, every region 256-byte aligned): 20 bytes per pair plus the
+// partial sums.
+struct TableBuildPlan : SortGrid {
+  uint64_t off_off = 0, off_bytes = 0;      // u64[n + 1]
+  uint64_t erel_off = 0, erel_bytes = 0;    // u64[n]
+  uint64_t es_off = 0, es_bytes = 0;        // u32[n + 2]
+  uint64_t sum_off = 0, sum_bytes = 0;      // u64[nwg]
+  uint64_t esum_off = 0, esum_bytes = 0;    // u64[nwg]
+  uint64_t flag_off = 0, flag_bytes = 0;    // u64[nwg]
+  uint64_t tot_off = 0, tot_bytes = 0;      // u64[4]
+  uint64_t seal_off = 0, seal_bytes = 0;    // the seal's descriptor: crc stream, out pointer, capacity
+  uint64_t bytes = 0;
+};
+
+inline uint32_t plan_table_build_wgs(uint32_t cus) { return std::max<uint32_t>(cus, 1) * kTbWgsPerCu; }
+
+inline int plan_table_build(uint64_t n, uint32_t max_wgs, TableBuildPlan& P) {
+  if (n > 0xffffffffull || max_wgs == 0) return DLSM_E_ARG;
+  P = TableBuildPlan();
+  static_cast<SortGrid&>(P) = sort_grid(n, kTbChunk, max_wgs);
+  P.nwg = std::max<uint32_t>(P.nwg, 1);
+  Layout ws;  // (the totals and the seal's descriptor first: their addresses do not move with n)
+  ws.region(&P.tot_off, &P.tot_bytes, sizeof(uint64_t) * 4);
+  ws.region(&P.seal_off, &P.seal_bytes, 64);
+  ws.region(&P.off_off, &P.off_bytes, sizeof(uint64_t) * (n + 1));
+  ws.region(&P.erel_off, &P.erel_bytes, sizeof(uint64_t) * n);
+  ws.region(&P.es_off, &P.es_bytes, sizeof(uint32_t) * (n + 2));
+  ws.region(&P.sum_off, &P.sum_bytes, sizeof(uint64_t) * P.nwg);
+  ws.region(&P.esum_off, &P.esum_bytes, sizeof(uint64_t) * P.nwg);
+  ws.region(&P.flag_off, &P.flag_bytes, sizeof(uint64_t) * P.nwg);
+  P.bytes = ws.at;
+  return DLSM_OK;
+}
+
+// dlsm_table_build_bound: the region's exact length and a capacity no index
+// block of n pairs passes (an entry: at most 5 + 1 + 1 header bytes, the key,
+// two 10-byte varints, a restart offset; then the count and the trailer).
+inline int plan_table_build_bound(uint64_t n, uint64_t key_bytes, uint64_t value_bytes, uint64_t* data_bytes,
+                                  uint64_t* index_cap) {
+  if (n > 0xffffffffull) return DLSM_E_ARG;
+  const uint64_t d = 8 * n + key_bytes + value_bytes, x = 31 * n + key_bytes + 9;
+  if (d < key_bytes || d < value_bytes || x < key_bytes) return DLSM_E_ARG;
+  if (data_bytes) *data_bytes = d;
+  if (index_cap) *index_cap = x;
+  return DLSM_OK;
+}
+
 }  // namespace plan
 }  // namespace dlsm

@@ -813,6 +813,97 @@ uint32_t dlsm_kv_read_span(void);
  * call). */
 int dlsm_kv_read_stats(const dlsm_ctx* ctx, double* launch_ms, uint32_t* copy_wgs);
 
+/* ---- table build: the data region and the sealed index block ------------- */
+
+/* What TableBuilder_BACS emits for a run of pairs besides the filter: the data
+ * region (Add, table/table_builder_bacs.cpp:221-226, cut into chunks by the
+ * flush rule at :186-189) and the sealed index block (one entry per pair
+ * through a BlockBuilder at restart interval 1, :195-206, sealed at :313-358),
+ * byte-exact, from keys and values that are already on the device.  The
+ * outputs open with dlsm_tableindex_create_blocks and dlsm_tabledata_create
+ * (chunks_are_device = 1, the chunk lengths from chunk_end).  Each output is a
+ * pure function of the inputs:
+ *   data: pair i is Fixed32 key_size | Fixed32 value_size | key | value at
+ *   offset[i], the exclusive sum of 8 + key_size + value_size over the pairs
+ *   before i; data_bytes is the total, exact whatever data_cap is;
+ *   chunk_end[c]: the running end of chunk c.  A new chunk starts before a pair
+ *   when the current chunk is not empty and its bytes + the pair > chunk_bytes
+ *   (a pair that fits exactly stays); a pair larger than chunk_bytes sits alone
+ *   in an oversize chunk and sets DLSM_TABLE_OVERSIZE_PAIR (the reference would
+ *   overrun its buffer there).  chunk_bytes = 0: one chunk.  n = 0: one chunk of
+ *   0 bytes.  n_chunks is exact whatever chunk_cap is;
+ *   index: entry i is 00 | varint32 key_size | value_len byte | key | varint64
+ *   offset[i] | varint64 size (8 + key_size + value_size); after the entries n
+ *   Fixed32 restart offsets and Fixed32 n; then [type 0][Fixed32 masked crc32c
+ *   of contents || type].  index_bytes is the sealed length, exact whatever
+ *   index_cap is; n = 0 gives the 9-byte block.
+ * flags: a capacity bit where data_bytes > data_cap, index_bytes > index_cap or
+ * n_chunks > chunk_cap: every byte below the cap is still the right one, except
+ * that the index block's 5-byte trailer is written only when the whole block
+ * fits.  With DLSM_TABLE_SHORT_KEY (a key of fewer than 8 bytes),
+ * DLSM_TABLE_PAIR_TOO_BIG (a pair whose size does not fit 32 bits) or
+ * DLSM_TABLE_INDEX_TOO_BIG (index contents past 4 GiB) only `built` is
+ * specified, and its n_chunks is 0: the chunks are not walked.  Nothing is ever written at or past a cap, past a total, or past
+ * chunk_end[min(n_chunks, chunk_cap)).
+ * The keys are written whole and in the caller's order: like BlockBuilder,
+ * which only asserts it, the build does not check that they ascend --
+ * dlsm_tableindex_create_blocks rejects a block whose keys do not.
+ * n = 0 is valid; n > UINT32_MAX returns DLSM_E_ARG.  DLSM_OPT_FAULT_INJECT
+ * makes the calls return the injected error.
+ * dlsm_table_build_dev: every pointer device memory; asynchronous on the
+ * context's stream: six launches whatever n is (size, offsets, region with the
+ * chunk chain, index, and the seal's two crc launches), no host read-back, no
+ * counter shared between workgroups.  The chunk chain is one hop per chunk in
+ * one wave beside the region write: its time is linear in n_chunks (about
+ * 0.7 us a hop on an MI355X), so a chunk_bytes far below a flush buffer's
+ * length makes the region launch as long as the chain.
+ * dlsm_table_build: every pointer host memory; the same rules run on the host
+ * (no device is touched; ctx may be NULL), synchronous. */
+#define DLSM_TABLE_DATA_CAP 1u
+#define DLSM_TABLE_INDEX_CAP 2u
+#define DLSM_TABLE_CHUNK_CAP 4u
+#define DLSM_TABLE_SHORT_KEY 8u
+#define DLSM_TABLE_PAIR_TOO_BIG 16u
+#define DLSM_TABLE_INDEX_TOO_BIG 32u
+#define DLSM_TABLE_OVERSIZE_PAIR 64u
+typedef struct {
+  dlsm_keyset keys;          /* internal keys in table order (user key || Fixed64 trailer), fixed or
+                                variable length; written whole; suffix_len is not looked at */
+  const uint8_t* values;     /* packed values */
+  const uint64_t* value_off; /* u64[n + 1], or NULL: every value is value_len bytes */
+  uint32_t value_len;
+  uint64_t chunk_bytes;      /* the flush buffer's length (local_data_mr[0]->length); 0: one chunk */
+} dlsm_table_input;
+typedef struct {
+  uint64_t data_bytes, index_bytes, n_chunks, flags;
+} dlsm_table_built;
+typedef struct {
+  uint8_t* data;       /* the region, offsets running on across chunks; 16-byte aligned */
+  uint64_t data_cap;
+  uint8_t* index;      /* [contents][type 0][masked crc32c]; 16-byte aligned */
+  uint64_t index_cap;
+  uint64_t* chunk_end; /* running chunk ends, the `end[]` of dlsm_tabledata_create */
+  uint64_t chunk_cap;
+  dlsm_table_built* built; /* written by the call (by the device for the _dev form) */
+} dlsm_table_output;
+
+int dlsm_table_build_dev(dlsm_ctx* ctx, const dlsm_table_input* in, const dlsm_table_output* out);
+int dlsm_table_build(dlsm_ctx* ctx, const dlsm_table_input* in, const dlsm_table_output* out);
+/* Host only: the region's exact length for n pairs of key_bytes and
+ * value_bytes in all, and an index capacity that no block of them passes. */
+int dlsm_table_build_bound(uint64_t n, uint64_t key_bytes, uint64_t value_bytes, uint64_t* data_bytes,
+                           uint64_t* index_cap);
+/* Pairs per workgroup chunk of the size and offset passes, and output bytes
+ * per workgroup step of the region write (the sizes around which the tests
+ * are built). */
+uint32_t dlsm_table_build_chunk(void);
+uint32_t dlsm_table_build_span(void);
+/* The last dlsm_table_build_dev of the context, once its work has completed:
+ * launch_ms[5] (or NULL) gets the device time of the size, offsets, region and
+ * index launches and of the seal, from events recorded around them; *write_wgs
+ * (or NULL) the persistent grid of the two writes. */
+int dlsm_table_build_stats(const dlsm_ctx* ctx, double* launch_ms, uint32_t* write_wgs);
+
 /* ---- legacy FilterPolicy format (util/bloom.cc) ------------------------- */
 
 /* CreateFilter(keys, n, dst) per job: writes bytes+1 bytes at out.
