@@ -35,6 +35,7 @@ __all__ = [
     "index_fence_interval", "index_seek_block", "index_block_check", "index_block_seek",
     "TableData", "kv_read_chunk", "kv_read_span", "kv_pair_read",
     "table_build", "table_build_chunk", "table_build_span", "table_build_bound",
+    "compaction_merge", "merge_tile", "merge_span", "merge_chunk", "MERGE_KEEP_ALL", "MERGE_DROP_HIDDEN",
 ]
 
 PATH_AUTO, PATH_DIRECT, PATH_SLICED = 0, 1, 2
@@ -180,6 +181,78 @@ def table_build(keys: "Keys", values: np.ndarray, *, value_off: Optional[np.ndar
     check(lib().dlsm_table_build(ctx.h if ctx is not None else None, C.byref(ti), C.byref(to)), "table_build")
     b = tuple(int(x) for x in built)
     return data[:min(b[0], data_cap)], index[:min(b[1], index_cap)], ends[:min(b[2], chunk_cap)], b
+
+
+MERGE_KEEP_ALL, MERGE_DROP_HIDDEN = 0, 1  # dlsm_compaction_merge policies
+MERGE_KEYS_CAP, MERGE_VALUES_CAP, MERGE_PAIR_CAP, MERGE_SHORT_KEY, MERGE_UNSORTED = 1, 2, 4, 8, 16
+
+
+def merge_tile() -> int:
+    """Records per workgroup step of a compaction merge pass."""
+    return int(lib().dlsm_merge_tile())
+
+
+def merge_span() -> int:
+    """Output bytes per workgroup step of the compaction merge's gather."""
+    return int(lib().dlsm_merge_span())
+
+
+def merge_chunk() -> int:
+    """Pairs per workgroup chunk of the compaction merge's record, decide and offset passes."""
+    return int(lib().dlsm_merge_chunk())
+
+
+def _merge_io(runs, keys, keys_cap, key_off, values, values_cap, value_off, src, pair_cap, merged):
+    """runs: (Keys, values, value_off or None, value_len) per sorted run."""
+    if not 1 <= len(runs) <= 64:
+        raise ValueError("compaction_merge: 1 to 64 runs")
+    mr = (_L.dlsm_merge_run * len(runs))()
+    for r, (k, v, vo, vl) in enumerate(runs):
+        if vo is not None:
+            _need(vo, 8 * (k.n + 1), "value_off")
+        else:
+            _need(v, k.n * vl, "values")
+        mr[r] = _L.dlsm_merge_run(k.c(), _ptr(v), _ptr(vo), vl)
+    keys_cap = _nbytes(keys) if keys_cap is None else int(keys_cap)
+    values_cap = _nbytes(values) if values_cap is None else int(values_cap)
+    pair_cap = max(_nbytes(key_off) // 8 - 1, 0) if pair_cap is None else int(pair_cap)
+    for x, nb, what in ((keys, keys_cap, "keys"), (values, values_cap, "values"), (key_off, 8 * (pair_cap + 1), "key_off"),
+                        (value_off, 8 * (pair_cap + 1), "value_off"), (merged, 40, "merged")):
+        _need(x, nb, what)
+    if src is not None:
+        _need(src, 8 * pair_cap, "src")
+    mo = _L.dlsm_merge_output(_ptr(keys), keys_cap, _ptr(key_off), _ptr(values), values_cap, _ptr(value_off), _ptr(src),
+                              pair_cap, _ptr(merged))
+    return mr, mo
+
+
+def compaction_merge(runs, policy: int = MERGE_DROP_HIDDEN, smallest_snapshot: int = 0, *,
+                     keys_cap: Optional[int] = None, values_cap: Optional[int] = None, pair_cap: Optional[int] = None,
+                     ctx: Optional["Context"] = None):
+    """The host form of the compaction merge (dlsm_compaction_merge; no device
+    is touched): ``runs`` is a list of (Keys, values, value_off or None,
+    value_len) over host arrays, each run sorted.  Returns (keys uint8,
+    key_off uint64, values uint8, value_off uint64, src uint64, merged) with
+    merged = (n_in, n_out, key_bytes, value_bytes, flags); the arrays are cut at
+    min(total, cap).  The caps default to what the inputs hold."""
+    def nb(x, off, n, ln):
+        return int(off[n] - off[0]) if off is not None else n * ln
+
+    n = sum(k.n for k, _, _, _ in runs)
+    kb = sum(nb(k.data, k.offsets, k.n, k.key_len) for k, _, _, _ in runs)
+    vb = sum(nb(v, vo, k.n, vl) for k, v, vo, vl in runs)
+    keys_cap = kb if keys_cap is None else int(keys_cap)
+    values_cap = vb if values_cap is None else int(values_cap)
+    pair_cap = n if pair_cap is None else int(pair_cap)
+    keys, values = np.zeros(max(keys_cap, 1), dtype=np.uint8), np.zeros(max(values_cap, 1), dtype=np.uint8)
+    key_off, value_off = np.zeros(pair_cap + 1, dtype=np.uint64), np.zeros(pair_cap + 1, dtype=np.uint64)
+    src, merged = np.zeros(max(pair_cap, 1), dtype=np.uint64), np.zeros(5, dtype=np.uint64)
+    mr, mo = _merge_io(runs, keys, keys_cap, key_off, values, values_cap, value_off, src, pair_cap, merged)
+    check(lib().dlsm_compaction_merge(ctx.h if ctx is not None else None, mr, len(runs), policy, smallest_snapshot,
+                                      C.byref(mo)), "compaction_merge")
+    m = tuple(int(x) for x in merged)
+    p = min(m[1], pair_cap)
+    return (keys[:min(m[2], keys_cap)], key_off[:p + 1], values[:min(m[3], values_cap)], value_off[:p + 1], src[:p], m)
 
 
 def kv_pair_read(chunks, handle, user_key: bytes, state: int = GET_FOUND):
@@ -1051,6 +1124,35 @@ class Context:
         ms, wgs = (C.c_double * 5)(), C.c_uint32()
         check(lib().dlsm_table_build_stats(self.h, ms, C.byref(wgs)), "table_build_stats")
         return tuple(float(x) for x in ms), int(wgs.value)
+
+    # -- compaction merge: sorted runs into one run ------------------------------
+    def compaction_merge_dev(self, runs, keys, key_off, values, value_off, merged, *, src=None,
+                             policy: int = MERGE_DROP_HIDDEN, smallest_snapshot: int = 0,
+                             keys_cap: Optional[int] = None, values_cap: Optional[int] = None,
+                             pair_cap: Optional[int] = None):
+        """Merge sorted runs on the device: ``runs`` is a list of (Keys, values,
+        value_off or None, value_len) over device tensors.  keys / values
+        (device uint8, 16-byte aligned) get the kept internal keys / values
+        back to back, key_off / value_off (device uint64[pair_cap + 1]) their
+        offsets, src (device uint64[pair_cap], optional) run << 32 | index per
+        output pair, merged (device uint64[5]) n_in, n_out, key_bytes,
+        value_bytes, flags.  The output is the table build's input form.  The
+        caps default to the buffers' lengths.  Asynchronous."""
+        mr, mo = _merge_io(runs, keys, keys_cap, key_off, values, values_cap, value_off, src, pair_cap, merged)
+        check(lib().dlsm_compaction_merge_dev(self.h, mr, len(runs), policy, smallest_snapshot, C.byref(mo)),
+              "compaction_merge_dev")
+
+    def compaction_merge(self, runs, policy: int = MERGE_DROP_HIDDEN, smallest_snapshot: int = 0, **kw):
+        """The host-memory form (see dlsm_amd.compaction_merge)."""
+        return compaction_merge(runs, policy, smallest_snapshot, ctx=self, **kw)
+
+    def compaction_merge_stats(self):
+        """(record, partition, merge, decide, offsets, gather) device
+        milliseconds of the last compaction_merge_dev (call after sync) and its
+        number of merge passes."""
+        ms, passes = (C.c_double * 6)(), C.c_uint32()
+        check(lib().dlsm_compaction_merge_stats(self.h, ms, C.byref(passes)), "compaction_merge_stats")
+        return tuple(float(x) for x in ms), int(passes.value)
 
     # -- full filter probe --------------------------------------------------
     def filterset(self, filters, on_device: bool = False, *, sealed: bool = False,

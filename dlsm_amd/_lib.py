@@ -72,6 +72,16 @@ class dlsm_table_output(C.Structure):
                 ("chunk_end", C.c_void_p), ("chunk_cap", C.c_uint64), ("built", C.c_void_p)]
 
 
+class dlsm_merge_run(C.Structure):
+    _fields_ = [("keys", dlsm_keyset), ("values", C.c_void_p), ("value_off", C.c_void_p), ("value_len", C.c_uint32)]
+
+
+class dlsm_merge_output(C.Structure):
+    _fields_ = [("keys", C.c_void_p), ("keys_cap", C.c_uint64), ("key_off", C.c_void_p), ("values", C.c_void_p),
+                ("values_cap", C.c_uint64), ("value_off", C.c_void_p), ("src", C.c_void_p), ("pair_cap", C.c_uint64),
+                ("merged", C.c_void_p)]
+
+
 class DlsmError(RuntimeError):
     def __init__(self, status: int, what: str = ""):
         self.status = status
@@ -209,6 +219,14 @@ SIGNATURES = [
     ("dlsm_table_build_chunk", C.c_uint32, []),
     ("dlsm_table_build_span", C.c_uint32, []),
     ("dlsm_table_build_stats", C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
+    ("dlsm_compaction_merge_dev", C.c_int, [_VP, C.POINTER(dlsm_merge_run), C.c_int, C.c_int, C.c_uint64,
+                                            C.POINTER(dlsm_merge_output)]),
+    ("dlsm_compaction_merge", C.c_int, [_VP, C.POINTER(dlsm_merge_run), C.c_int, C.c_int, C.c_uint64,
+                                        C.POINTER(dlsm_merge_output)]),
+    ("dlsm_merge_tile", C.c_uint32, []),
+    ("dlsm_merge_span", C.c_uint32, []),
+    ("dlsm_merge_chunk", C.c_uint32, []),
+    ("dlsm_compaction_merge_stats", C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
     ("dlsm_bloom_full_probe", C.c_int, [_VP, _VP, C.POINTER(dlsm_keyset), _VP]),
     ("dlsm_bloom_full_probe_hashed_dev", C.c_int, [_VP, _VP, C.POINTER(dlsm_keyset), _VP]),
     ("dlsm_bloom_hash_batch", C.c_int, [C.POINTER(dlsm_keyset), _VP, C.c_int]),

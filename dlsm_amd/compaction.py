@@ -1,0 +1,46 @@
+"""The compaction merge in pure Python (never calls the library).
+
+``MergingIterator`` (table/merger.cc:178-199) over the compaction's inputs
+yields every pair in ``InternalKeyComparator::Compare`` order
+(db/dbformat.cc:41-57): user keys ascending under ``Slice::compare`` -- which is
+Python's ``bytes`` ordering -- and, within one user key, trailers descending;
+``FindSmallest``'s strict ``<`` gives equal keys to the lower child first.  The
+loop of ``DBImpl::DoCompactionWork`` (db/db_impl.cc:3500-3562) then drops what
+rule (A) hides.  This module restates both so tests and callers can check the
+device and host forms of ``dlsm_compaction_merge``.
+"""
+import struct
+
+KEEP_ALL, DROP_HIDDEN = 0, 1
+MAX_SEQUENCE = (1 << 56) - 1  # kMaxSequenceNumber (db/dbformat.h)
+
+
+def trailer(ikey: bytes) -> int:
+    return struct.unpack("<Q", ikey[-8:])[0]
+
+
+def merge_runs(runs, policy=DROP_HIDDEN, snapshot=0):
+    """runs: a list of runs, each a list of (internal key, value) in the run's
+    order.  Returns (pairs, src): the surviving (internal key, value) in merged
+    order and, per pair, run << 32 | index in run."""
+    items = sorted(((ik[:-8], -trailer(ik), r, i) for r, run in enumerate(runs) for i, (ik, _) in enumerate(run)))
+    pairs, src = [], []
+    # last_seq is None where the reference holds kMaxSequenceNumber: "no earlier
+    # entry of this user key" (a first occurrence is never hidden, as in
+    # DLSM_SELECT_COMPACTION, even under a snapshot of kMaxSequenceNumber)
+    has_current, current, last_seq = False, None, None
+    for user, _, r, i in items:
+        ik, value = runs[r][i]
+        t = trailer(ik)
+        drop = False
+        if (t & 0xff) > 1:  # ParseInternalKey fails: "do not hide error keys"
+            has_current, current, last_seq = False, None, None
+        else:
+            if not has_current or user != current:
+                has_current, current, last_seq = True, user, None
+            drop = policy == DROP_HIDDEN and last_seq is not None and last_seq <= snapshot  # rule (A)
+            last_seq = t >> 8
+        if not drop:
+            pairs.append((ik, value))
+            src.append(r << 32 | i)
+    return pairs, src

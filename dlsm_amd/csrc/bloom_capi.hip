@@ -166,6 +166,10 @@ struct dlsm_ctx {
   const uint8_t* tb_seal_index = nullptr;  // table build: the block whose seal descriptor lies in tb_ws ...
   uint64_t tb_seal_cap = 0, tb_seal_gen = 0;  // ... its capacity, and tb_ws's generation then
   hipStream_t tb_seal_stream = nullptr;       // ... and the stream the descriptor went up on
+  DevBuf<uint8_t> cm_ws;      // compaction merge: table, records, offsets, partial sums (plan::CompactionMergePlan's layout)
+  hipEvent_t ev_cm[2 * kCmMaxPasses + 5] = {};  // compaction merge: around every launch (dlsm_compaction_merge_stats)
+  uint32_t cm_passes = 0;     // ... the last call's merge passes
+  bool cm_timed = false;      // ... which recorded all of its events
   int cus = 0;               // the device's compute units (0: not asked yet)
   // host-API staging
   DevBuf<uint8_t> st_keys;
@@ -596,6 +600,7 @@ int dlsm_ctx_destroy(dlsm_ctx* ctx) {
   ctx->route_ws.release();
   ctx->kv_ws.release();
   ctx->tb_ws.release();
+  ctx->cm_ws.release();
   ctx->sel.release();
   ctx->st_keys.release();
   ctx->st_offs.release();
@@ -615,6 +620,8 @@ int dlsm_ctx_destroy(dlsm_ctx* ctx) {
   for (hipEvent_t e : ctx->ev_kv)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->ev_tb)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : ctx->ev_cm)
     if (e) (void)hipEventDestroy(e);
   if (ctx->ev_ing0) (void)hipEventDestroy(ctx->ev_ing0);
   if (ctx->ev_ing1) (void)hipEventDestroy(ctx->ev_ing1);
@@ -825,7 +832,7 @@ int dlsm_ctx_stats(dlsm_ctx* ctx, uint64_t* device_allocs, uint64_t* device_byte
   add(ctx->vgl); add(ctx->vabyte); add(ctx->vplan); add(ctx->plan_ws); add(ctx->route_ws);
   add(ctx->st_keys); add(ctx->st_offs); add(ctx->st_out); add(ctx->st_len); add(ctx->st_filter);
   add(ctx->crc_streams); add(ctx->crc_partial); add(ctx->crc_tabs); add(ctx->crc_outp); add(ctx->crc_cap);
-  add(ctx->crc_val); add(ctx->sel); add(ctx->kv_ws); add(ctx->tb_ws);
+  add(ctx->crc_val); add(ctx->sel); add(ctx->kv_ws); add(ctx->tb_ws); add(ctx->cm_ws);
   if (device_allocs) *device_allocs = n;
   if (device_bytes) *device_bytes = b;
   return DLSM_OK;
@@ -3255,6 +3262,194 @@ int dlsm_table_build(dlsm_ctx* ctx, const dlsm_table_input* in, const dlsm_table
     const uint32_t m = dlsm_crc32c_mask(dlsm_crc32c_extend(0, out->index, ctot + 1));
     memcpy(out->index + ctot + 1, &m, 4);
   }
+  return DLSM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Compaction merge: sorted runs into one run, hidden entries dropped, keys and
+// values packed (MergingIterator, table/merger.cc:178-199; DoCompactionWork,
+// db/db_impl.cc:3500-3562; compaction_merge.hip)
+// ---------------------------------------------------------------------------
+uint32_t dlsm_merge_tile(void) { return kCmTile; }
+uint32_t dlsm_merge_span(void) { return kCmSpan; }
+uint32_t dlsm_merge_chunk(void) { return kCmChunk; }
+
+// The arguments' checks and the plan with its runs filled in.
+static int compaction_merge_plan(const dlsm_merge_run* runs, int n_runs, int policy, const dlsm_merge_output* out,
+                                 CompactionMergePlan& P) {
+  if (!runs || n_runs < 1 || n_runs > static_cast<int>(kCmMaxRuns) || !out || !out->merged || !out->key_off ||
+      !out->value_off || (policy != DLSM_MERGE_KEEP_ALL && policy != DLSM_MERGE_DROP_HIDDEN))
+    return DLSM_E_ARG;
+  if ((out->keys_cap && !out->keys) || (out->values_cap && !out->values)) return DLSM_E_ARG;
+  uint64_t run_n[kCmMaxRuns];
+  for (int r = 0; r < n_runs; r++) {
+    DLSM_CHECK(validate_keyset(runs[r].keys));
+    if (runs[r].keys.n && !runs[r].values && (runs[r].value_off || runs[r].value_len)) return DLSM_E_ARG;
+    run_n[r] = runs[r].keys.n;
+  }
+  DLSM_CHECK(plan_compaction_merge(run_n, n_runs, kSortMaxWgs, P));
+  for (int r = 0; r < n_runs; r++) {
+    CmRun& d = P.tab.runs[r];
+    d.kbytes = runs[r].keys.bytes;
+    d.koff = runs[r].keys.offsets;
+    d.klen = runs[r].keys.key_len;
+    d.vbytes = runs[r].values;
+    d.voff = runs[r].value_off;
+    d.vlen = runs[r].value_len;
+  }
+  return DLSM_OK;
+}
+
+int dlsm_compaction_merge_dev(dlsm_ctx* ctx, const dlsm_merge_run* runs, int n_runs, int policy,
+                              uint64_t smallest_snapshot, const dlsm_merge_output* out) {
+  if (!ctx) return DLSM_E_ARG;
+  CompactionMergePlan P;
+  DLSM_CHECK(compaction_merge_plan(runs, n_runs, policy, out, P));
+  if (!aligned(out->keys, 16) || !aligned(out->values, 16) || !aligned(out->key_off, 8) || !aligned(out->value_off, 8) ||
+      !aligned(out->src, 8) || !aligned(out->merged, 8))
+    return DLSM_E_ARG;
+  for (int r = 0; r < n_runs; r++)
+    if (!aligned(runs[r].keys.offsets, 8) || !aligned(runs[r].value_off, 8)) return DLSM_E_ARG;
+  if (ctx->fault) return -ctx->fault;
+  DeviceGuard g(ctx->device);
+  if (!ctx->cus) {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || cus <= 0)
+      cus = kTbWgs / kTbWgsPerCu;
+    ctx->cus = cus;
+  }
+  for (hipEvent_t& e : ctx->ev_cm)
+    if (!e) DLSM_TRY(hipEventCreate(&e));
+  ctx->cm_timed = false;
+  DLSM_CHECK(ctx->cm_ws.ensure(P.bytes));
+  uint8_t* ws = ctx->cm_ws.p;
+  DLSM_CHECK(ctx_upload(ctx, ws + P.tab_off, &P.tab, sizeof(CmTable), ctx->stream));
+  auto u64 = [&](uint64_t off) { return reinterpret_cast<uint64_t*>(ws + off); };
+  CmDev a{};
+  a.tab = reinterpret_cast<const CmTable*>(ws + P.tab_off);
+  a.n = P.n;
+  a.n_runs = P.tab.n_runs;
+  a.n_passes = P.tab.n_passes;
+  a.policy = policy;
+  a.snapshot = smallest_snapshot;
+  a.rec[0] = reinterpret_cast<CmRec*>(ws + P.rec_off[0]);
+  a.rec[1] = reinterpret_cast<CmRec*>(ws + P.rec_off[1]);
+  a.split = reinterpret_cast<uint32_t*>(ws + P.split_off);
+  a.wko = u64(P.ko_off);
+  a.wvo = u64(P.vo_off);
+  a.wg_flags = u64(P.flag_off);
+  a.wg_cnt = u64(P.cnt_off);
+  a.wg_kb = u64(P.kb_off);
+  a.wg_vb = u64(P.vb_off);
+  a.tot = u64(P.tot_off);
+  a.keys = out->keys;
+  a.keys_cap = out->keys_cap;
+  a.key_off = out->key_off;
+  a.values = out->values;
+  a.values_cap = out->values_cap;
+  a.value_off = out->value_off;
+  a.src = out->src;
+  a.pair_cap = out->pair_cap;
+  a.merged = reinterpret_cast<uint64_t*>(out->merged);
+  a.cpw = P.cpw;
+  a.nwg = P.nwg;
+  a.copy_wgs = plan_table_build_wgs(static_cast<uint32_t>(ctx->cus));
+  DLSM_TRY(launch_compaction_merge(a, P.tab.tiles, ctx->ev_cm, ctx->stream));
+  ctx->cm_passes = P.tab.n_passes;
+  ctx->cm_timed = true;
+  return DLSM_OK;
+}
+
+int dlsm_compaction_merge_stats(const dlsm_ctx* ctx, double* launch_ms, uint32_t* passes) {
+  if (!ctx) return DLSM_E_ARG;
+  if (passes) *passes = ctx->cm_passes;
+  if (launch_ms) {
+    for (uint32_t j = 0; j < kCmLaunchKinds; j++) launch_ms[j] = 0;
+    if (!ctx->cm_timed) return DLSM_OK;
+    DeviceGuard g(ctx->device);
+    const uint32_t launches = 2 * ctx->cm_passes + 4;
+    for (uint32_t j = 0; j < launches; j++) {
+      float ms = 0;
+      DLSM_TRY(hipEventElapsedTime(&ms, ctx->ev_cm[j], ctx->ev_cm[j + 1]));
+      // record | (partition, merge) per pass | decide, offsets, gather
+      const uint32_t tail = launches - 3;
+      const uint32_t kind = j == 0 ? 0 : (j < tail ? 1 + ((j - 1) & 1) : 3 + (j - tail));
+      launch_ms[kind] += ms;
+    }
+  }
+  return DLSM_OK;
+}
+
+// The host form: the passes of compaction_merge.hip one after the other on
+// the host, tile by tile and lane by lane through the same functions of
+// compaction_merge.h.
+int dlsm_compaction_merge(dlsm_ctx* ctx, const dlsm_merge_run* runs, int n_runs, int policy,
+                          uint64_t smallest_snapshot, const dlsm_merge_output* out) {
+  CompactionMergePlan P;
+  DLSM_CHECK(compaction_merge_plan(runs, n_runs, policy, out, P));
+  if (ctx && ctx->fault) return -ctx->fault;
+  const CmTable& T = P.tab;
+  const uint64_t n = P.n;
+  std::vector<CmRec> buf[2] = {std::vector<CmRec>(n), std::vector<CmRec>(n)};
+  uint64_t flags = 0;
+  for (uint32_t r = 0; r < T.n_runs; r++) {
+    bool sk, prev_ok = false;  // a neighbour with a short key is not compared
+    for (uint64_t i = 0, m = T.base[r + 1] - T.base[r]; i < m; i++, prev_ok = !sk) {
+      CmRec& cur = buf[0][T.base[r] + i];
+      cur = cm_record(T.runs[r], r, i, &sk);
+      if (sk) flags |= kCmShortKey;
+      else if (prev_ok && cm_rec_cmp(buf[0][T.base[r] + i - 1], cur, T.runs) >= 0) flags |= kCmUnsorted;
+    }
+  }
+  if (flags) {
+    *out->merged = dlsm_merged{n, 0, 0, 0, flags};
+    return DLSM_OK;
+  }
+  for (uint32_t pass = 0; pass < T.n_passes; pass++) {
+    const CmRec* in = buf[pass & 1].data();
+    CmRec* to = buf[(pass & 1) ^ 1].data();
+    for (uint32_t k = T.pair0[pass]; k < T.pair0[pass + 1]; k++) {
+      const CmPair& p = T.pairs[k];
+      const uint32_t na_all = p.b0 - p.a0, nb_all = p.b1 - p.b0, len = na_all + nb_all;
+      for (uint64_t d0 = 0; d0 < len; d0 += kCmTile) {
+        const uint32_t d1 = static_cast<uint32_t>(std::min<uint64_t>(d0 + kCmTile, len));
+        const uint32_t a_lo = cm_path_split(in + p.a0, na_all, in + p.b0, nb_all, static_cast<uint32_t>(d0), T.runs);
+        const uint32_t a_hi = d1 == len ? na_all : cm_path_split(in + p.a0, na_all, in + p.b0, nb_all, d1, T.runs);
+        const uint32_t b_lo = static_cast<uint32_t>(d0) - a_lo, na = a_hi - a_lo, cnt = d1 - static_cast<uint32_t>(d0);
+        for (uint32_t o0 = 0; o0 < cnt; o0 += kCmLane)
+          cm_merge_lane(in + p.a0 + a_lo, na, in + p.b0 + b_lo, cnt - na, o0, std::min(kCmLane, cnt - o0),
+                        to + p.a0 + d0 + o0, T.runs);
+      }
+    }
+  }
+  const std::vector<CmRec>& rec = buf[T.n_passes & 1];
+  uint64_t j = 0, ko = 0, vo = 0;
+  for (uint64_t i = 0; i < n; i++) {
+    const CmRec& cur = rec[i];
+    if (policy != DLSM_MERGE_KEEP_ALL && i > 0 && cm_hidden(rec[i - 1], cur, smallest_snapshot, T.runs)) continue;
+    const CmRun& r = T.runs[cm_run(cur)];
+    const uint64_t ks = r.key_size(cm_index(cur)), vs = r.value_size(cm_index(cur));
+    if (j <= out->pair_cap) {
+      out->key_off[j] = ko;
+      out->value_off[j] = vo;
+    }
+    if (out->src && j < out->pair_cap) out->src[j] = cm_src(cur);
+    if (ko < out->keys_cap)
+      memcpy(out->keys + ko, reinterpret_cast<const uint8_t*>(r.key_src(cm_index(cur))), std::min(ks, out->keys_cap - ko));
+    if (vs && vo < out->values_cap)
+      memcpy(out->values + vo, reinterpret_cast<const uint8_t*>(r.value_src(cm_index(cur))),
+             std::min(vs, out->values_cap - vo));
+    j++;
+    ko += ks;
+    vo += vs;
+  }
+  if (j <= out->pair_cap) {
+    out->key_off[j] = ko;
+    out->value_off[j] = vo;
+  }
+  *out->merged = dlsm_merged{n, j, ko, vo,
+                             (ko > out->keys_cap ? kCmKeysCap : 0) | (vo > out->values_cap ? kCmValuesCap : 0) |
+                                 (j > out->pair_cap ? kCmPairCap : 0)};
   return DLSM_OK;
 }
 

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "bloom_math.h"
+#include "compaction_merge.h"
 #include "index_seek.h"
 #include "kv_read.h"
 #include "read_plan.h"
@@ -546,5 +547,40 @@ struct TbDev {
 };
 // ev: five events recorded around the four launches, or nullptr.
 hipError_t launch_table_build(const TbDev& a, uint32_t index_wgs, hipEvent_t* ev, hipStream_t s);
+
+// compaction_merge.hip: R sorted runs into one run in the table build's input
+// form (dlsm_compaction_merge_dev).  Workspace in plan::CompactionMergePlan's
+// layout; the record buffer the last pass did not write holds the decide
+// pass's lengths and the gather's source addresses (4 x u64[n]).
+struct CmDev {
+  const CmTable* tab;  // workspace: the runs, their bases, the passes' pairs
+  uint64_t n;          // input pairs
+  uint32_t n_runs, n_passes;
+  int policy;
+  uint64_t snapshot;
+  CmRec* rec[2];       // workspace CmRec[n] each: pass p reads rec[p & 1] and writes the other
+  uint32_t* split;     // workspace u32[most tiles of a pass + 1]: the left segment's share in front of each tile
+  uint64_t* wko;       // workspace u64[n + 1]: the kept keys' offsets and the total
+  uint64_t* wvo;       // workspace u64[n + 1]: ... the values'
+  uint64_t* wg_flags;  // workspace u64[nwg]: the record pass's bits per workgroup
+  uint64_t* wg_cnt;    // workspace u64[nwg]: kept pairs per workgroup
+  uint64_t* wg_kb;     // workspace u64[nwg]: kept key bytes per workgroup
+  uint64_t* wg_vb;     // workspace u64[nwg]: kept value bytes per workgroup
+  uint64_t* tot;       // workspace u64[4]: n_out, key bytes, value bytes, the record pass's bits
+  uint8_t* keys;       // 16-byte aligned
+  uint64_t keys_cap;
+  uint64_t* key_off;
+  uint8_t* values;     // 16-byte aligned
+  uint64_t values_cap;
+  uint64_t* value_off;
+  uint64_t* src;       // or nullptr
+  uint64_t pair_cap;
+  uint64_t* merged;    // dlsm_merged: n_in, n_out, key_bytes, value_bytes, flags
+  uint32_t cpw, nwg;   // plan::sort_grid(n, kCmChunk, kSortMaxWgs), at least one workgroup
+  uint32_t copy_wgs;   // the gather's persistent grid
+};
+// tiles[p]: pass p's tiles (CmTable::tiles); ev: an event around every launch
+// (2 * n_passes + 5 of them), or nullptr.
+hipError_t launch_compaction_merge(const CmDev& a, const uint32_t* tiles, hipEvent_t* ev, hipStream_t s);
 
 }  // namespace dlsm

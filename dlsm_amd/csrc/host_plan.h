@@ -1075,5 +1075,74 @@ inline int plan_table_build_bound(uint64_t n, uint64_t key_bytes, uint64_t value
   return DLSM_OK;
 }
 
+// ---- compaction merge (compaction_merge.hip) -----------------------------------
+// dlsm_compaction_merge_dev from the runs' pair counts alone: the runs' bases,
+// ceil(log2 R) passes of two-way merges -- pass p pairs neighbouring segments
+// of 2^p runs, an unpaired segment is a pair with an empty right side -- each
+// pair's output cut into tiles of kCmTile records; the per-pair grid of the
+// record, decide and offset passes (one workgroup where there is no pair: it
+// writes the totals); and the workspace layout (byte offsets, every region
+// 256-byte aligned): 80 bytes per pair plus the table and the partial sums.
+// tab.runs is left to the caller.
+struct CompactionMergePlan : SortGrid {
+  CmTable tab;
+  uint64_t n = 0;
+  uint32_t max_tiles = 0;                  // the most tiles of one pass
+  uint64_t tab_off = 0, tab_bytes = 0;     // CmTable
+  uint64_t tot_off = 0, tot_bytes = 0;     // u64[4]
+  uint64_t rec_off[2] = {0, 0}, rec_bytes = 0;  // CmRec[n] twice
+  uint64_t split_off = 0, split_bytes = 0;  // u32[max_tiles + 1]
+  uint64_t ko_off = 0, vo_off = 0, off_bytes = 0;  // u64[n + 1] twice
+  uint64_t flag_off = 0, cnt_off = 0, kb_off = 0, vb_off = 0, wg_bytes = 0;  // u64[nwg] four times
+  uint64_t bytes = 0;
+};
+
+inline int plan_compaction_merge(const uint64_t* run_n, int n_runs, uint32_t max_wgs, CompactionMergePlan& P) {
+  if (!run_n || n_runs < 1 || n_runs > static_cast<int>(kCmMaxRuns) || max_wgs == 0) return DLSM_E_ARG;
+  P = CompactionMergePlan();
+  CmTable& T = P.tab;
+  const uint32_t R = static_cast<uint32_t>(n_runs);
+  for (uint32_t r = 0; r < R; r++) {
+    T.base[r] = P.n;
+    P.n += run_n[r];
+    if (P.n < run_n[r] || P.n > 0xffffffffull) return DLSM_E_ARG;
+  }
+  for (uint32_t r = R; r <= kCmMaxRuns; r++) T.base[r] = P.n;
+  T.n_runs = R;
+  uint32_t pairs = 0;
+  for (T.n_passes = 0; (1u << T.n_passes) < R; T.n_passes++) {
+    const uint32_t w = 1u << T.n_passes;
+    T.pair0[T.n_passes] = pairs;
+    uint64_t tiles = 0;
+    for (uint32_t s = 0; s < R; s += 2 * w) {
+      CmPair& p = T.pairs[pairs++];
+      p.a0 = static_cast<uint32_t>(T.base[s]);
+      p.b0 = static_cast<uint32_t>(T.base[std::min(s + w, R)]);
+      p.b1 = static_cast<uint32_t>(T.base[std::min(s + 2 * w, R)]);
+      p.tile0 = static_cast<uint32_t>(tiles);
+      tiles += (static_cast<uint64_t>(p.b1) - p.a0 + kCmTile - 1) / kCmTile;
+    }
+    T.tiles[T.n_passes] = static_cast<uint32_t>(tiles);
+    P.max_tiles = std::max(P.max_tiles, T.tiles[T.n_passes]);
+  }
+  for (uint32_t p = T.n_passes; p <= kCmMaxPasses; p++) T.pair0[p] = pairs;
+  static_cast<SortGrid&>(P) = sort_grid(P.n, kCmChunk, max_wgs);
+  P.nwg = std::max<uint32_t>(P.nwg, 1);
+  Layout ws;
+  ws.region(&P.tab_off, &P.tab_bytes, sizeof(CmTable));
+  ws.region(&P.tot_off, &P.tot_bytes, sizeof(uint64_t) * 4);
+  ws.region(&P.rec_off[0], &P.rec_bytes, sizeof(CmRec) * P.n);
+  ws.region(&P.rec_off[1], &P.rec_bytes, sizeof(CmRec) * P.n);
+  ws.region(&P.split_off, &P.split_bytes, sizeof(uint32_t) * (static_cast<uint64_t>(P.max_tiles) + 1));
+  ws.region(&P.ko_off, &P.off_bytes, sizeof(uint64_t) * (P.n + 1));
+  ws.region(&P.vo_off, &P.off_bytes, sizeof(uint64_t) * (P.n + 1));
+  ws.region(&P.flag_off, &P.wg_bytes, sizeof(uint64_t) * P.nwg);
+  ws.region(&P.cnt_off, &P.wg_bytes, sizeof(uint64_t) * P.nwg);
+  ws.region(&P.kb_off, &P.wg_bytes, sizeof(uint64_t) * P.nwg);
+  ws.region(&P.vb_off, &P.wg_bytes, sizeof(uint64_t) * P.nwg);
+  P.bytes = ws.at;
+  return DLSM_OK;
+}
+
 }  // namespace plan
 }  // namespace dlsm

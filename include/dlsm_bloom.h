@@ -904,6 +904,102 @@ uint32_t dlsm_table_build_span(void);
  * (or NULL) the persistent grid of the two writes. */
 int dlsm_table_build_stats(const dlsm_ctx* ctx, double* launch_ms, uint32_t* write_wgs);
 
+/* ---- compaction merge: sorted runs into one run, hidden entries dropped --- */
+
+/* What MergingIterator (table/merger.cc:178-199) over MakeInputIterator's
+ * children (db/version_set.cc:1565-1596) hands to the loop of
+ * DBImpl::DoCompactionWork (db/db_impl.cc:3500-3562), that loop's drop rule
+ * (A), and the surviving pairs packed in the table build's input form: R runs
+ * in, one run out.  Each output is a pure function of the inputs:
+ *   order: the output sequence is the total order of
+ *   InternalKeyComparator::Compare (db/dbformat.cc:41-57): user keys ascend
+ *   under Slice::compare (memcmp over the common length, then the shorter key
+ *   first), and within one user key the Fixed64 trailers descend as numbers.
+ *   Two inputs that compare equal leave in ascending run number, then ascending
+ *   index (FindSmallest's strict < keeps the lower child); src[j] = run << 32 |
+ *   index in run of output pair j shows it;
+ *   drop: DLSM_MERGE_KEEP_ALL keeps every pair.  DLSM_MERGE_DROP_HIDDEN applies
+ *   DLSM_SELECT_COMPACTION's rule to merged positions: pair i is dropped iff it
+ *   parses (type <= 1), pair i-1 -- its predecessor in merged order, dropped or
+ *   not (last_sequence_for_key) -- parses and has the same user key, and
+ *   seq(i-1) <= smallest_snapshot.  A key of type > 1 is kept and restarts its
+ *   user key.  Rule (B) is commented out in the reference and is not applied;
+ *   merged: n_in the input pairs, n_out the kept ones, key_bytes / value_bytes
+ *   their totals, all exact whatever the caps are;
+ *   key_off[j] / value_off[j]: the exclusive sums of the kept keys' / values'
+ *   lengths, written for j <= min(n_out, pair_cap); keys / values: the kept
+ *   keys (whole internal keys) / values back to back.
+ * flags: a capacity bit where key_bytes > keys_cap, value_bytes > values_cap or
+ * n_out > pair_cap: every byte of keys and values below min(total, cap) is
+ * still the right one.  Nothing is ever written at or past a cap, past a
+ * total, or past src[min(n_out, pair_cap)).  With DLSM_MERGE_SHORT_KEY (some
+ * key has fewer than 8 bytes) or DLSM_MERGE_UNSORTED (two neighbours of one run
+ * do not strictly ascend under the comparator -- the check
+ * dlsm_tableindex_create_blocks applies to a block) only `merged` is written,
+ * of it only n_in and flags are specified, and no key or value is read through
+ * or walked any further.
+ * A run with n = 0 is valid; 1 <= n_runs <= 64, and n_runs = 1 is a plain
+ * (optionally dropping) repack; more than UINT32_MAX pairs in all returns
+ * DLSM_E_ARG.  key_off, value_off and merged are required, src may be NULL.
+ * DLSM_OPT_FAULT_INJECT makes the calls return the injected error.
+ * dlsm_compaction_merge_dev: every pointer inside runs[] and out device memory
+ * (runs[] and *out themselves host memory); asynchronous on the context's
+ * stream: 2 * ceil(log2 n_runs) + 4 launches whatever the runs hold (record,
+ * a partition and a merge per pass, decide, offsets, gather), no host
+ * read-back, no counter shared between workgroups, no result that depends on
+ * the order of atomics.  A caller that needs n_out on the host for
+ * dlsm_table_build_dev reads `merged` (40 bytes) once; with KEEP_ALL n_out =
+ * n_in needs no read.
+ * dlsm_compaction_merge: every pointer host memory; the same rules run on the
+ * host (no device is touched; ctx may be NULL), synchronous. */
+typedef struct {            /* one sorted run: dlsm_table_input without chunk_bytes */
+  dlsm_keyset keys;         /* internal keys, fixed or variable length; suffix_len is not looked at */
+  const uint8_t* values;    /* packed values */
+  const uint64_t* value_off;/* u64[n + 1], or NULL: every value is value_len bytes */
+  uint32_t value_len;
+} dlsm_merge_run;
+
+#define DLSM_MERGE_KEEP_ALL 0    /* every input pair, merged */
+#define DLSM_MERGE_DROP_HIDDEN 1 /* rule (A): the rule of DLSM_SELECT_COMPACTION */
+
+#define DLSM_MERGE_KEYS_CAP 1u
+#define DLSM_MERGE_VALUES_CAP 2u
+#define DLSM_MERGE_PAIR_CAP 4u
+#define DLSM_MERGE_SHORT_KEY 8u
+#define DLSM_MERGE_UNSORTED 16u
+
+typedef struct {
+  uint64_t n_in, n_out, key_bytes, value_bytes, flags;
+} dlsm_merged;
+typedef struct {
+  uint8_t* keys;       /* packed internal keys; 16-byte aligned */
+  uint64_t keys_cap;
+  uint64_t* key_off;   /* u64[pair_cap + 1] */
+  uint8_t* values;     /* packed values; 16-byte aligned */
+  uint64_t values_cap;
+  uint64_t* value_off; /* u64[pair_cap + 1] */
+  uint64_t* src;       /* u64[pair_cap] or NULL: run << 32 | index in run per output pair */
+  uint64_t pair_cap;
+  dlsm_merged* merged; /* written by the call (by the device for the _dev form) */
+} dlsm_merge_output;
+
+int dlsm_compaction_merge_dev(dlsm_ctx* ctx, const dlsm_merge_run* runs, int n_runs, int policy,
+                              uint64_t smallest_snapshot, const dlsm_merge_output* out);
+int dlsm_compaction_merge(dlsm_ctx* ctx, const dlsm_merge_run* runs, int n_runs, int policy,
+                          uint64_t smallest_snapshot, const dlsm_merge_output* out);
+/* Records per workgroup step of a merge pass, output bytes per workgroup step
+ * of the gather, and pairs per workgroup chunk of the record, decide and
+ * offset passes (the sizes around which the tests are built). */
+uint32_t dlsm_merge_tile(void);
+uint32_t dlsm_merge_span(void);
+uint32_t dlsm_merge_chunk(void);
+/* The last dlsm_compaction_merge_dev of the context, once its work has
+ * completed: launch_ms[6] (or NULL) gets the device time per launch kind --
+ * record, partition (all passes), merge (all passes), decide, offsets, gather
+ * -- from events recorded around the launches; *passes (or NULL) the number
+ * of merge passes. */
+int dlsm_compaction_merge_stats(const dlsm_ctx* ctx, double* launch_ms, uint32_t* passes);
+
 /* ---- legacy FilterPolicy format (util/bloom.cc) ------------------------- */
 
 /* CreateFilter(keys, n, dst) per job: writes bytes+1 bytes at out.
