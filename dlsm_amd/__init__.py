@@ -36,6 +36,7 @@ __all__ = [
     "TableData", "kv_read_chunk", "kv_read_span", "kv_pair_read",
     "table_build", "table_build_chunk", "table_build_span", "table_build_bound",
     "compaction_merge", "merge_tile", "merge_span", "merge_chunk", "MERGE_KEEP_ALL", "MERGE_DROP_HIDDEN",
+    "compaction_merge_tables", "MERGE_TABLE_MISMATCH",
 ]
 
 PATH_AUTO, PATH_DIRECT, PATH_SLICED = 0, 1, 2
@@ -185,6 +186,7 @@ def table_build(keys: "Keys", values: np.ndarray, *, value_off: Optional[np.ndar
 
 MERGE_KEEP_ALL, MERGE_DROP_HIDDEN = 0, 1  # dlsm_compaction_merge policies
 MERGE_KEYS_CAP, MERGE_VALUES_CAP, MERGE_PAIR_CAP, MERGE_SHORT_KEY, MERGE_UNSORTED = 1, 2, 4, 8, 16
+MERGE_TABLE_MISMATCH = 32
 
 
 def merge_tile() -> int:
@@ -213,6 +215,10 @@ def _merge_io(runs, keys, keys_cap, key_off, values, values_cap, value_off, src,
         else:
             _need(v, k.n * vl, "values")
         mr[r] = _L.dlsm_merge_run(k.c(), _ptr(v), _ptr(vo), vl)
+    return mr, _merge_out(keys, keys_cap, key_off, values, values_cap, value_off, src, pair_cap, merged)
+
+
+def _merge_out(keys, keys_cap, key_off, values, values_cap, value_off, src, pair_cap, merged):
     keys_cap = _nbytes(keys) if keys_cap is None else int(keys_cap)
     values_cap = _nbytes(values) if values_cap is None else int(values_cap)
     pair_cap = max(_nbytes(key_off) // 8 - 1, 0) if pair_cap is None else int(pair_cap)
@@ -223,7 +229,52 @@ def _merge_io(runs, keys, keys_cap, key_off, values, values_cap, value_off, src,
         _need(src, 8 * pair_cap, "src")
     mo = _L.dlsm_merge_output(_ptr(keys), keys_cap, _ptr(key_off), _ptr(values), values_cap, _ptr(value_off), _ptr(src),
                               pair_cap, _ptr(merged))
-    return mr, mo
+    return mo
+
+
+def _table_runs(runs):
+    """runs: a list of file-number lists.  Returns (dlsm_table_run array, what it points into)."""
+    keep = [np.ascontiguousarray(r, dtype=np.uint32) for r in runs]
+    tr = (_L.dlsm_table_run * max(len(runs), 1))()
+    for r, a in enumerate(keep):
+        tr[r] = _L.dlsm_table_run(a.ctypes.data_as(C.POINTER(C.c_uint32)) if a.size else None, a.size)
+    return tr, keep
+
+
+def compaction_merge_tables(blocks, files, runs, policy: int = MERGE_DROP_HIDDEN, smallest_snapshot: int = 0, *,
+                            keys_cap: int, values_cap: int, pair_cap: int, ctx: Optional["Context"] = None):
+    """The host form of the merge out of tables (dlsm_compaction_merge_tables;
+    no device is touched): ``blocks[f]`` is file f's sealed index block (bytes)
+    or None, ``files[f]`` the list of its data chunks (bytes) as for TableIndex
+    and TableData, ``runs`` a list of file-number lists -- a level-0 file each,
+    or a deeper level's files in key order.  The caps size the outputs.
+    Returns what compaction_merge returns, src counting through each run's
+    concatenated files."""
+    n = len(blocks)
+    if len(files) != n:
+        raise ValueError("compaction_merge_tables: one chunk list per block")
+    bk = [None if b is None else np.frombuffer(bytes(b) + b"\0", dtype=np.uint8) for b in blocks]
+    pa = (C.c_void_p * max(n, 1))(*[None if a is None else a.ctypes.data for a in bk])
+    la = (C.c_uint64 * max(n, 1))(*[0 if a is None else a.size - 1 for a in bk])
+    begin = np.zeros(n + 1, dtype=np.uint32)
+    ck, recs = [], []
+    for f, chunks in enumerate(files):
+        for c in (chunks or []):
+            ck.append(np.frombuffer(bytes(c) + b"\0", dtype=np.uint8))
+            recs.append(_L.dlsm_data_chunk(ck[-1].ctypes.data, ck[-1].size - 1))
+        begin[f + 1] = len(recs)
+    ca = (_L.dlsm_data_chunk * max(len(recs), 1))(*recs)
+    tr, _keep = _table_runs(runs)
+    keys, values = np.zeros(max(keys_cap, 1), dtype=np.uint8), np.zeros(max(values_cap, 1), dtype=np.uint8)
+    key_off, value_off = np.zeros(pair_cap + 1, dtype=np.uint64), np.zeros(pair_cap + 1, dtype=np.uint64)
+    src, merged = np.zeros(max(pair_cap, 1), dtype=np.uint64), np.zeros(5, dtype=np.uint64)
+    mo = _merge_out(keys, keys_cap, key_off, values, values_cap, value_off, src, pair_cap, merged)
+    check(lib().dlsm_compaction_merge_tables(ctx.h if ctx is not None else None, pa, la, ca,
+                                             begin.ctypes.data_as(C.POINTER(C.c_uint32)), n, tr, len(runs), policy,
+                                             smallest_snapshot, C.byref(mo)), "compaction_merge_tables")
+    m = tuple(int(x) for x in merged)
+    p = min(m[1], pair_cap)
+    return (keys[:min(m[2], keys_cap)], key_off[:p + 1], values[:min(m[3], values_cap)], value_off[:p + 1], src[:p], m)
 
 
 def compaction_merge(runs, policy: int = MERGE_DROP_HIDDEN, smallest_snapshot: int = 0, *,
@@ -1146,10 +1197,31 @@ class Context:
         """The host-memory form (see dlsm_amd.compaction_merge)."""
         return compaction_merge(runs, policy, smallest_snapshot, ctx=self, **kw)
 
+    def compaction_merge_tables_dev(self, ti: "TableIndex", td: "TableData", runs, keys, key_off, values, value_off,
+                                    merged, *, src=None, policy: int = MERGE_DROP_HIDDEN, smallest_snapshot: int = 0,
+                                    keys_cap: Optional[int] = None, values_cap: Optional[int] = None,
+                                    pair_cap: Optional[int] = None):
+        """compaction_merge_dev with its inputs read straight out of the opened
+        tables ``ti`` / ``td``: ``runs`` is a list of file-number lists, a
+        level-0 file each or a deeper level's files in key order; a run's pairs
+        are its files' entries in the order listed.  The outputs are
+        compaction_merge_dev's, src counting through each run's concatenated
+        files.  Asynchronous."""
+        tr, _keep = _table_runs(runs)
+        mo = _merge_out(keys, keys_cap, key_off, values, values_cap, value_off, src, pair_cap, merged)
+        check(lib().dlsm_compaction_merge_tables_dev(self.h, ti.h, td.h, tr, len(runs), policy, smallest_snapshot,
+                                                     C.byref(mo)), "compaction_merge_tables_dev")
+
+    def compaction_merge_tables(self, blocks, files, runs, policy: int = MERGE_DROP_HIDDEN, smallest_snapshot: int = 0,
+                                **kw):
+        """The host-memory form (see dlsm_amd.compaction_merge_tables)."""
+        return compaction_merge_tables(blocks, files, runs, policy, smallest_snapshot, ctx=self, **kw)
+
     def compaction_merge_stats(self):
         """(record, partition, merge, decide, offsets, gather) device
-        milliseconds of the last compaction_merge_dev (call after sync) and its
-        number of merge passes."""
+        milliseconds of the last compaction_merge_dev or
+        compaction_merge_tables_dev (call after sync) and its number of merge
+        passes."""
         ms, passes = (C.c_double * 6)(), C.c_uint32()
         check(lib().dlsm_compaction_merge_stats(self.h, ms, C.byref(passes)), "compaction_merge_stats")
         return tuple(float(x) for x in ms), int(passes.value)

@@ -76,6 +76,10 @@ class dlsm_merge_run(C.Structure):
     _fields_ = [("keys", dlsm_keyset), ("values", C.c_void_p), ("value_off", C.c_void_p), ("value_len", C.c_uint32)]
 
 
+class dlsm_table_run(C.Structure):
+    _fields_ = [("files", C.POINTER(C.c_uint32)), ("n_files", C.c_uint32)]
+
+
 class dlsm_merge_output(C.Structure):
     _fields_ = [("keys", C.c_void_p), ("keys_cap", C.c_uint64), ("key_off", C.c_void_p), ("values", C.c_void_p),
                 ("values_cap", C.c_uint64), ("value_off", C.c_void_p), ("src", C.c_void_p), ("pair_cap", C.c_uint64),
@@ -223,6 +227,11 @@ SIGNATURES = [
                                             C.POINTER(dlsm_merge_output)]),
     ("dlsm_compaction_merge", C.c_int, [_VP, C.POINTER(dlsm_merge_run), C.c_int, C.c_int, C.c_uint64,
                                         C.POINTER(dlsm_merge_output)]),
+    ("dlsm_compaction_merge_tables_dev", C.c_int, [_VP, _VP, _VP, C.POINTER(dlsm_table_run), C.c_int, C.c_int, C.c_uint64,
+                                                   C.POINTER(dlsm_merge_output)]),
+    ("dlsm_compaction_merge_tables", C.c_int, [_VP, C.POINTER(_VP), _U64P, C.POINTER(dlsm_data_chunk),
+                                               C.POINTER(C.c_uint32), C.c_int, C.POINTER(dlsm_table_run), C.c_int, C.c_int,
+                                               C.c_uint64, C.POINTER(dlsm_merge_output)]),
     ("dlsm_merge_tile", C.c_uint32, []),
     ("dlsm_merge_span", C.c_uint32, []),
     ("dlsm_merge_chunk", C.c_uint32, []),

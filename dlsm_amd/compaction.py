@@ -19,6 +19,40 @@ def trailer(ikey: bytes) -> int:
     return struct.unpack("<Q", ikey[-8:])[0]
 
 
+def _varint(buf, p):
+    v = shift = 0
+    while True:
+        b = buf[p]
+        p += 1
+        v |= (b & 127) << shift
+        shift += 7
+        if b < 128:
+            return v, p
+
+
+def table_pairs(index_contents: bytes, chunks):
+    """One table as a compaction reads it (ByteAddressableSEQIterator,
+    table/byte_addressable_SEQ_iterrator.cpp:48-184): the index block's
+    contents give the entry count and, through the first entry's handle, the
+    first pair's offset; from there the pairs are walked back to back through
+    the chunks by their two Fixed32 lengths.  No other handle is looked at.
+    Returns the (internal key, value) list."""
+    n = struct.unpack("<I", index_contents[-4:])[0]
+    if n == 0:
+        return []
+    _, p = _varint(index_contents, 0)       # shared
+    klen, p = _varint(index_contents, p)    # non_shared
+    _, p = _varint(index_contents, p)       # value_len
+    at, _ = _varint(index_contents, p + klen)  # the handle's offset
+    region = b"".join(chunks)               # offsets run on across the chunks
+    pairs = []
+    for _ in range(n):
+        ks, vs = struct.unpack("<II", region[at:at + 8])
+        pairs.append((region[at + 8:at + 8 + ks], region[at + 8 + ks:at + 8 + ks + vs]))
+        at += 8 + ks + vs
+    return pairs
+
+
 def merge_runs(runs, policy=DROP_HIDDEN, snapshot=0):
     """runs: a list of runs, each a list of (internal key, value) in the run's
     order.  Returns (pairs, src): the surviving (internal key, value) in merged

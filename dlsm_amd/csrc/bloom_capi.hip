@@ -2638,6 +2638,8 @@ struct dlsm_tableindex {
   IndexFileDev* files = nullptr;  // n_files records
   RoutePrefix* fence = nullptr;   // the fence table
   uint64_t* slot0 = nullptr;      // the open's slot prefix sums
+  std::vector<uint32_t> file_n;   // host copy: every file's entries, as the open read them back
+  std::vector<uint8_t> held;      // host copy: the file's index is held
 };
 
 // The device half of the open: copy + crc (the ingest pass), the validation
@@ -2676,9 +2678,13 @@ static int tableindex_open(dlsm_ctx* ctx, const uint8_t* const* blocks, const ui
   if (n_files) DLSM_TRY(hipMemcpyAsync(h.data(), ti->files, sizeof(IndexFileDev) * n_files, hipMemcpyDeviceToHost, s));
   DLSM_TRY(ctx_sync(ctx, s));
   int ret = DLSM_OK;
+  ti->file_n.assign(n_files, 0);
+  ti->held.assign(n_files, 0);
   for (int f = 0; f < n_files; f++) {
     st[f] = DLSM_BLOCK_OK;
     if (!blocks[f]) continue;
+    ti->file_n[f] = h[f].n;
+    ti->held[f] = 1;
     const uint32_t r = recs[P.rec[f]].status;
     st[f] = static_cast<uint8_t>(r != DLSM_INGEST_OK ? r : (h[f].bad ? DLSM_BLOCK_INDEX : DLSM_BLOCK_OK));
     if (st[f] != DLSM_BLOCK_OK) ret = DLSM_E_CORRUPT;
@@ -2844,6 +2850,7 @@ struct dlsm_tabledata {
   uint8_t* tables = nullptr;  // [chunk_begin | end | base], each region 256-byte aligned
   uint8_t* arena = nullptr;   // host chunks' copies
   KvTables t{};
+  std::vector<uint32_t> chunk_begin;  // host copy of t.chunk_begin
 };
 
 int dlsm_tabledata_create(dlsm_ctx* ctx, const dlsm_data_chunk* chunks, const uint32_t* chunk_begin, int n_files,
@@ -2860,6 +2867,7 @@ int dlsm_tabledata_create(dlsm_ctx* ctx, const dlsm_data_chunk* chunks, const ui
   td->device = ctx->device;
   td->n_files = n_files;
   td->n_chunks = P.end.size();
+  td->chunk_begin.assign(chunk_begin, chunk_begin + n_files + 1);
   const uint64_t nc = td->n_chunks;
   auto run = [&]() -> int {
     hipStream_t s = ctx->stream;
@@ -3300,17 +3308,18 @@ static int compaction_merge_plan(const dlsm_merge_run* runs, int n_runs, int pol
   return DLSM_OK;
 }
 
-int dlsm_compaction_merge_dev(dlsm_ctx* ctx, const dlsm_merge_run* runs, int n_runs, int policy,
-                              uint64_t smallest_snapshot, const dlsm_merge_output* out) {
-  if (!ctx) return DLSM_E_ARG;
-  CompactionMergePlan P;
-  DLSM_CHECK(compaction_merge_plan(runs, n_runs, policy, out, P));
-  if (!aligned(out->keys, 16) || !aligned(out->values, 16) || !aligned(out->key_off, 8) || !aligned(out->value_off, 8) ||
-      !aligned(out->src, 8) || !aligned(out->merged, 8))
-    return DLSM_E_ARG;
-  for (int r = 0; r < n_runs; r++)
-    if (!aligned(runs[r].keys.offsets, 8) || !aligned(runs[r].value_off, 8)) return DLSM_E_ARG;
-  if (ctx->fault) return -ctx->fault;
+static bool merge_output_aligned(const dlsm_merge_output* out) {
+  return aligned(out->keys, 16) && aligned(out->values, 16) && aligned(out->key_off, 8) && aligned(out->value_off, 8) &&
+         aligned(out->src, 8) && aligned(out->merged, 8);
+}
+
+// The device half of both merge calls: the workspace, the tables' upload and
+// the launches.  tables: the runs are files of the opened tables ti / td -- P
+// is then that CompactionTablesPlan, and its runs' descriptor arrays are filled
+// in here, where the workspace is known.
+static int compaction_merge_launch(dlsm_ctx* ctx, CompactionMergePlan& P, int policy, uint64_t smallest_snapshot,
+                                   const dlsm_merge_output* out, const CompactionTablesPlan* tables,
+                                   const dlsm_tableindex* ti, const dlsm_tabledata* td) {
   DeviceGuard g(ctx->device);
   if (!ctx->cus) {
     int cus = 0;
@@ -3323,6 +3332,16 @@ int dlsm_compaction_merge_dev(dlsm_ctx* ctx, const dlsm_merge_run* runs, int n_r
   ctx->cm_timed = false;
   DLSM_CHECK(ctx->cm_ws.ensure(P.bytes));
   uint8_t* ws = ctx->cm_ws.p;
+  TsDev t{};
+  if (tables) {
+    t.ts = reinterpret_cast<const TsTable*>(ws + tables->ts_off);
+    t.files = ti->files;
+    t.tables = td->t;
+    t.desc = reinterpret_cast<CmDesc*>(ws + tables->desc_off);
+    t.n_listed = tables->ts.n_listed;
+    for (uint32_t r = 0; r < P.tab.n_runs; r++) P.tab.runs[r].desc = t.desc + P.tab.base[r];
+    DLSM_CHECK(ctx_upload(ctx, ws + tables->ts_off, &tables->ts, sizeof(TsTable), ctx->stream));
+  }
   DLSM_CHECK(ctx_upload(ctx, ws + P.tab_off, &P.tab, sizeof(CmTable), ctx->stream));
   auto u64 = [&](uint64_t off) { return reinterpret_cast<uint64_t*>(ws + off); };
   CmDev a{};
@@ -3354,10 +3373,48 @@ int dlsm_compaction_merge_dev(dlsm_ctx* ctx, const dlsm_merge_run* runs, int n_r
   a.cpw = P.cpw;
   a.nwg = P.nwg;
   a.copy_wgs = plan_table_build_wgs(static_cast<uint32_t>(ctx->cus));
-  DLSM_TRY(launch_compaction_merge(a, P.tab.tiles, ctx->ev_cm, ctx->stream));
+  DLSM_TRY(launch_compaction_merge(a, P.tab.tiles, ctx->ev_cm, ctx->stream, tables ? &t : nullptr));
   ctx->cm_passes = P.tab.n_passes;
   ctx->cm_timed = true;
   return DLSM_OK;
+}
+
+int dlsm_compaction_merge_dev(dlsm_ctx* ctx, const dlsm_merge_run* runs, int n_runs, int policy,
+                              uint64_t smallest_snapshot, const dlsm_merge_output* out) {
+  if (!ctx) return DLSM_E_ARG;
+  CompactionMergePlan P;
+  DLSM_CHECK(compaction_merge_plan(runs, n_runs, policy, out, P));
+  if (!merge_output_aligned(out)) return DLSM_E_ARG;
+  for (int r = 0; r < n_runs; r++)
+    if (!aligned(runs[r].keys.offsets, 8) || !aligned(runs[r].value_off, 8)) return DLSM_E_ARG;
+  if (ctx->fault) return -ctx->fault;
+  return compaction_merge_launch(ctx, P, policy, smallest_snapshot, out, nullptr, nullptr, nullptr);
+}
+
+// The output's checks of the two tables forms.
+static int merge_tables_output_ok(const dlsm_merge_output* out, int policy) {
+  if (!out || !out->merged || !out->key_off || !out->value_off ||
+      (policy != DLSM_MERGE_KEEP_ALL && policy != DLSM_MERGE_DROP_HIDDEN))
+    return DLSM_E_ARG;
+  if ((out->keys_cap && !out->keys) || (out->values_cap && !out->values)) return DLSM_E_ARG;
+  return DLSM_OK;
+}
+
+int dlsm_compaction_merge_tables_dev(dlsm_ctx* ctx, const dlsm_tableindex* ti, const dlsm_tabledata* td,
+                                     const dlsm_table_run* runs, int n_runs, int policy, uint64_t smallest_snapshot,
+                                     const dlsm_merge_output* out) {
+  if (!ctx || !ti || !td || ti->device != ctx->device || td->device != ctx->device || ti->n_files != td->n_files)
+    return DLSM_E_ARG;
+  DLSM_CHECK(merge_tables_output_ok(out, policy));
+  const uint32_t nf = static_cast<uint32_t>(ti->n_files);
+  std::vector<uint8_t> held(nf);  // an index, and chunks for its entries
+  for (uint32_t f = 0; f < nf; f++)
+    held[f] = ti->held[f] && (ti->file_n[f] == 0 || td->chunk_begin[f + 1] > td->chunk_begin[f]);
+  CompactionTablesPlan P;
+  DLSM_CHECK(plan_compaction_tables(ti->file_n.data(), held.data(), nf, runs, n_runs, kSortMaxWgs, P));
+  if (!merge_output_aligned(out)) return DLSM_E_ARG;
+  if (ctx->fault) return -ctx->fault;
+  return compaction_merge_launch(ctx, P, policy, smallest_snapshot, out, &P, ti, td);
 }
 
 int dlsm_compaction_merge_stats(const dlsm_ctx* ctx, double* launch_ms, uint32_t* passes) {
@@ -3380,6 +3437,67 @@ int dlsm_compaction_merge_stats(const dlsm_ctx* ctx, double* launch_ms, uint32_t
   return DLSM_OK;
 }
 
+// What follows the record pass, on the host: buf[0] holds the inputs' records,
+// flags that pass's bits.  D: the runs are in the descriptor form.
+extern "C++" {
+template <bool D>
+static int compaction_merge_host(const CompactionMergePlan& P, std::vector<CmRec>* buf, uint64_t flags, int policy,
+                                 uint64_t smallest_snapshot, const dlsm_merge_output* out) {
+  const CmTable& T = P.tab;
+  const uint64_t n = P.n;
+  if (flags) {
+    *out->merged = dlsm_merged{n, 0, 0, 0, flags};
+    return DLSM_OK;
+  }
+  for (uint32_t pass = 0; pass < T.n_passes; pass++) {
+    const CmRec* in = buf[pass & 1].data();
+    CmRec* to = buf[(pass & 1) ^ 1].data();
+    for (uint32_t k = T.pair0[pass]; k < T.pair0[pass + 1]; k++) {
+      const CmPair& p = T.pairs[k];
+      const uint32_t na_all = p.b0 - p.a0, nb_all = p.b1 - p.b0, len = na_all + nb_all;
+      for (uint64_t d0 = 0; d0 < len; d0 += kCmTile) {
+        const uint32_t d1 = static_cast<uint32_t>(std::min<uint64_t>(d0 + kCmTile, len));
+        const uint32_t a_lo = cm_path_split<D>(in + p.a0, na_all, in + p.b0, nb_all, static_cast<uint32_t>(d0), T.runs);
+        const uint32_t a_hi = d1 == len ? na_all : cm_path_split<D>(in + p.a0, na_all, in + p.b0, nb_all, d1, T.runs);
+        const uint32_t b_lo = static_cast<uint32_t>(d0) - a_lo, na = a_hi - a_lo, cnt = d1 - static_cast<uint32_t>(d0);
+        for (uint32_t o0 = 0; o0 < cnt; o0 += kCmLane)
+          cm_merge_lane<D>(in + p.a0 + a_lo, na, in + p.b0 + b_lo, cnt - na, o0, std::min(kCmLane, cnt - o0),
+                        to + p.a0 + d0 + o0, T.runs);
+      }
+    }
+  }
+  const std::vector<CmRec>& rec = buf[T.n_passes & 1];
+  uint64_t j = 0, ko = 0, vo = 0;
+  for (uint64_t i = 0; i < n; i++) {
+    const CmRec& cur = rec[i];
+    if (policy != DLSM_MERGE_KEEP_ALL && i > 0 && cm_hidden<D>(rec[i - 1], cur, smallest_snapshot, T.runs)) continue;
+    const CmPairAt q = cm_pair_at<D>(T.runs[cm_run(cur)], cm_index(cur));
+    const uint64_t ks = q.key_size, vs = q.value_size;
+    if (j <= out->pair_cap) {
+      out->key_off[j] = ko;
+      out->value_off[j] = vo;
+    }
+    if (out->src && j < out->pair_cap) out->src[j] = cm_src(cur);
+    if (ko < out->keys_cap)
+      memcpy(out->keys + ko, reinterpret_cast<const uint8_t*>(q.key_src), std::min(ks, out->keys_cap - ko));
+    if (vs && vo < out->values_cap)
+      memcpy(out->values + vo, reinterpret_cast<const uint8_t*>(q.value_src),
+             std::min(vs, out->values_cap - vo));
+    j++;
+    ko += ks;
+    vo += vs;
+  }
+  if (j <= out->pair_cap) {
+    out->key_off[j] = ko;
+    out->value_off[j] = vo;
+  }
+  *out->merged = dlsm_merged{n, j, ko, vo,
+                             (ko > out->keys_cap ? kCmKeysCap : 0) | (vo > out->values_cap ? kCmValuesCap : 0) |
+                                 (j > out->pair_cap ? kCmPairCap : 0)};
+  return DLSM_OK;
+}
+}  // extern "C++"
+
 // The host form: the passes of compaction_merge.hip one after the other on
 // the host, tile by tile and lane by lane through the same functions of
 // compaction_merge.h.
@@ -3401,56 +3519,69 @@ int dlsm_compaction_merge(dlsm_ctx* ctx, const dlsm_merge_run* runs, int n_runs,
       else if (prev_ok && cm_rec_cmp(buf[0][T.base[r] + i - 1], cur, T.runs) >= 0) flags |= kCmUnsorted;
     }
   }
-  if (flags) {
-    *out->merged = dlsm_merged{n, 0, 0, 0, flags};
-    return DLSM_OK;
+  return compaction_merge_host<false>(P, buf, flags, policy, smallest_snapshot, out);
+}
+
+// The seal and the open's checks of one sealed index block on the host
+// (dlsm_tableindex_create_blocks' rules): its contents' view, or false.
+static bool index_block_open_host(const uint8_t* block, uint64_t len, IndexView* v) {
+  if (len < 5 || block[len - 5] != 0) return false;  // kNoCompression
+  uint32_t stored;
+  memcpy(&stored, block + len - 4, 4);
+  if (dlsm_crc32c_mask(dlsm_crc32c_extend(0, block, len - 4)) != stored) return false;
+  if (!index_header_valid(block, len - 5, v)) return false;
+  for (uint32_t i = 0; i < v->n; i++)
+    if (!index_entry_valid(*v, i)) return false;
+  return true;
+}
+
+// The host form of the tables merge: table_scan.h's rule entry by entry in the
+// place of table_scan.hip, then the passes as above.  A listed block that would
+// not open returns DLSM_E_CORRUPT.
+int dlsm_compaction_merge_tables(dlsm_ctx* ctx, const uint8_t* const* blocks, const uint64_t* lens,
+                                 const dlsm_data_chunk* chunks, const uint32_t* chunk_begin, int n_files,
+                                 const dlsm_table_run* runs, int n_runs, int policy, uint64_t smallest_snapshot,
+                                 const dlsm_merge_output* out) {
+  if (n_files < 0 || (n_files > 0 && (!blocks || !lens))) return DLSM_E_ARG;
+  DLSM_CHECK(merge_tables_output_ok(out, policy));
+  TableDataPlan data;
+  DLSM_CHECK(plan_tabledata(chunks, chunk_begin, n_files, data));
+  const uint32_t nf = static_cast<uint32_t>(n_files);
+  std::vector<TsFile> file(nf);
+  std::vector<uint32_t> file_n(nf, 0);
+  std::vector<uint8_t> held(nf, 0);
+  std::vector<const uint8_t*> base(data.end.size());
+  for (size_t c = 0; c < base.size(); c++) base[c] = chunks[c].base;
+  for (uint32_t f = 0; f < nf; f++) {
+    const uint32_t c0 = chunk_begin[f], c1 = chunk_begin[f + 1];
+    file[f].chunks = KvChunks{data.end.data() + c0, base.data() + c0, c1 - c0};
+    // (the count alone, for the plan: a header that does not parse has none and fails the open below)
+    if (blocks[f] && lens[f] >= 5) (void)index_header_valid(blocks[f], lens[f] - 5, &file[f].index);
+    else file[f].index = IndexView{nullptr, 0, 0};
+    file_n[f] = file[f].index.n;
+    held[f] = blocks[f] && (file_n[f] == 0 || c1 > c0);
   }
-  for (uint32_t pass = 0; pass < T.n_passes; pass++) {
-    const CmRec* in = buf[pass & 1].data();
-    CmRec* to = buf[(pass & 1) ^ 1].data();
-    for (uint32_t k = T.pair0[pass]; k < T.pair0[pass + 1]; k++) {
-      const CmPair& p = T.pairs[k];
-      const uint32_t na_all = p.b0 - p.a0, nb_all = p.b1 - p.b0, len = na_all + nb_all;
-      for (uint64_t d0 = 0; d0 < len; d0 += kCmTile) {
-        const uint32_t d1 = static_cast<uint32_t>(std::min<uint64_t>(d0 + kCmTile, len));
-        const uint32_t a_lo = cm_path_split(in + p.a0, na_all, in + p.b0, nb_all, static_cast<uint32_t>(d0), T.runs);
-        const uint32_t a_hi = d1 == len ? na_all : cm_path_split(in + p.a0, na_all, in + p.b0, nb_all, d1, T.runs);
-        const uint32_t b_lo = static_cast<uint32_t>(d0) - a_lo, na = a_hi - a_lo, cnt = d1 - static_cast<uint32_t>(d0);
-        for (uint32_t o0 = 0; o0 < cnt; o0 += kCmLane)
-          cm_merge_lane(in + p.a0 + a_lo, na, in + p.b0 + b_lo, cnt - na, o0, std::min(kCmLane, cnt - o0),
-                        to + p.a0 + d0 + o0, T.runs);
-      }
+  CompactionTablesPlan P;
+  DLSM_CHECK(plan_compaction_tables(file_n.data(), held.data(), nf, runs, n_runs, kSortMaxWgs, P));
+  if (ctx && ctx->fault) return -ctx->fault;
+  const TsTable& S = P.ts;
+  for (uint32_t k = 0; k < S.n_listed; k++)
+    if (!index_block_open_host(blocks[S.file[k]], lens[S.file[k]], &file[S.file[k]].index)) return DLSM_E_CORRUPT;
+  const uint64_t n = P.n;
+  std::vector<CmDesc> desc(n);
+  std::vector<CmRec> buf[2] = {std::vector<CmRec>(n), std::vector<CmRec>(n)};
+  for (uint32_t r = 0; r < P.tab.n_runs; r++) P.tab.runs[r].desc = desc.data() + P.tab.base[r];
+  uint64_t flags = 0;
+  uint32_t pk = 0, pi = 0;  // input g - 1
+  for (uint32_t k = 0; k < S.n_listed; k++) {
+    for (uint32_t i = 0; i < file_n[S.file[k]]; i++) {
+      const uint64_t g = S.ebase[k] + i, idx = g - P.tab.base[S.run[k]];
+      flags |= ts_entry(file[S.file[k]], i, idx > 0, file[S.file[pk]], pi, S.run[k], idx, &desc[g], &buf[0][g]);
+      pk = k;
+      pi = i;
     }
   }
-  const std::vector<CmRec>& rec = buf[T.n_passes & 1];
-  uint64_t j = 0, ko = 0, vo = 0;
-  for (uint64_t i = 0; i < n; i++) {
-    const CmRec& cur = rec[i];
-    if (policy != DLSM_MERGE_KEEP_ALL && i > 0 && cm_hidden(rec[i - 1], cur, smallest_snapshot, T.runs)) continue;
-    const CmRun& r = T.runs[cm_run(cur)];
-    const uint64_t ks = r.key_size(cm_index(cur)), vs = r.value_size(cm_index(cur));
-    if (j <= out->pair_cap) {
-      out->key_off[j] = ko;
-      out->value_off[j] = vo;
-    }
-    if (out->src && j < out->pair_cap) out->src[j] = cm_src(cur);
-    if (ko < out->keys_cap)
-      memcpy(out->keys + ko, reinterpret_cast<const uint8_t*>(r.key_src(cm_index(cur))), std::min(ks, out->keys_cap - ko));
-    if (vs && vo < out->values_cap)
-      memcpy(out->values + vo, reinterpret_cast<const uint8_t*>(r.value_src(cm_index(cur))),
-             std::min(vs, out->values_cap - vo));
-    j++;
-    ko += ks;
-    vo += vs;
-  }
-  if (j <= out->pair_cap) {
-    out->key_off[j] = ko;
-    out->value_off[j] = vo;
-  }
-  *out->merged = dlsm_merged{n, j, ko, vo,
-                             (ko > out->keys_cap ? kCmKeysCap : 0) | (vo > out->values_cap ? kCmValuesCap : 0) |
-                                 (j > out->pair_cap ? kCmPairCap : 0)};
-  return DLSM_OK;
+  return compaction_merge_host<true>(P, buf, flags, policy, smallest_snapshot, out);
 }
 
 // ---------------------------------------------------------------------------

@@ -12,6 +12,7 @@
 #include "read_plan.h"
 #include "shard_route.h"
 #include "table_build.h"
+#include "table_scan.h"
 
 namespace dlsm {
 
@@ -579,8 +580,23 @@ struct CmDev {
   uint32_t cpw, nwg;   // plan::sort_grid(n, kCmChunk, kSortMaxWgs), at least one workgroup
   uint32_t copy_wgs;   // the gather's persistent grid
 };
+// table_scan.hip: the record pass of a merge whose runs are files of opened
+// tables (dlsm_compaction_merge_tables_dev).  It stands where the packed runs'
+// record pass stands and leaves, besides the records and the workgroups' bits,
+// a descriptor per input: the runs of CmTable are in the descriptor form.
+struct TsDev {
+  const TsTable* ts;          // workspace: the listed files' bases, numbers and runs
+  const IndexFileDev* files;  // the tableindex's records
+  KvTables tables;            // the tabledata's chunk tables
+  CmDesc* desc;               // workspace CmDesc[n]: input g's pair
+  uint32_t n_listed;
+};
+hipError_t launch_table_record(const CmDev& a, const TsDev& t, hipStream_t s);
+
 // tiles[p]: pass p's tiles (CmTable::tiles); ev: an event around every launch
-// (2 * n_passes + 5 of them), or nullptr.
-hipError_t launch_compaction_merge(const CmDev& a, const uint32_t* tiles, hipEvent_t* ev, hipStream_t s);
+// (2 * n_passes + 5 of them), or nullptr; ts: the runs are files of opened
+// tables, or nullptr: packed runs.
+hipError_t launch_compaction_merge(const CmDev& a, const uint32_t* tiles, hipEvent_t* ev, hipStream_t s,
+                                   const TsDev* ts = nullptr);
 
 }  // namespace dlsm

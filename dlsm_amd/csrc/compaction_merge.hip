@@ -45,6 +45,11 @@
 // in LDS, each lane owns whole 16-byte units (kv_copy_unit: no header, so the
 // value read's unit serves), aligned non-temporal stores, no byte read outside
 // the input keys and values.
+//
+// Runs that are files of opened tables (dlsm_compaction_merge_tables_dev) take
+// the same launches with table_scan.hip's record pass in the first one's place:
+// every kernel that reads a pair through its run is instantiated per run form
+// (D: the descriptor form), so the packed forms' kernels are the ones they were.
 #include <hip/hip_runtime.h>
 
 #include "bloom_internal.h"
@@ -132,17 +137,21 @@ __device__ __forceinline__ void block_scan3(uint64_t* v, uint64_t (*sh)[kCmWaves
 // pass where there is no merge pass -- ORs the workgroups' words (`reduce`) and
 // its workgroup 0 leaves the result in tot[3]; every later launch reads that
 // one word.
+// A table record pass has kCmTableMismatch where the packed one has
+// kCmShortKey.
+template <bool D = false>
 __device__ __forceinline__ uint64_t cm_input_flags(const CmDev& a, bool reduce) {
   if (!reduce) return a.tot[3];
+  constexpr uint64_t kFirst = D ? kCmTableMismatch : kCmShortKey;
   int shortk = 0, unsorted = 0;
   for (uint32_t j = threadIdx.x; j < a.nwg; j += blockDim.x) {
     const uint64_t f = a.wg_flags[j];
-    shortk |= (f & kCmShortKey) != 0;
+    shortk |= (f & kFirst) != 0;
     unsorted |= (f & kCmUnsorted) != 0;
   }
   shortk = __syncthreads_or(shortk);
   unsorted = __syncthreads_or(unsorted);
-  const uint64_t flags = (shortk ? kCmShortKey : 0) | (unsorted ? kCmUnsorted : 0);
+  const uint64_t flags = (shortk ? kFirst : 0) | (unsorted ? kCmUnsorted : 0);
   if (blockIdx.x == 0 && threadIdx.x == 0) a.tot[3] = flags;
   return flags;
 }
@@ -195,8 +204,9 @@ __device__ __forceinline__ CmPair cm_pair_of(const CmTable* tab, uint32_t pass, 
   return tab->pairs[k];
 }
 
+template <bool D>
 __global__ __launch_bounds__(kCmTileLanes) void cm_partition_kernel(CmDev a, uint32_t pass, uint32_t ntiles) {
-  if (cm_input_flags(a, pass == 0)) return;
+  if (cm_input_flags<D>(a, pass == 0)) return;
   const uint32_t t = blockIdx.x * kCmTileLanes + threadIdx.x;
   if (t >= ntiles) return;
   const CmPair p = cm_pair_of(a.tab, pass, t);
@@ -204,9 +214,10 @@ __global__ __launch_bounds__(kCmTileLanes) void cm_partition_kernel(CmDev a, uin
   const uint64_t d = static_cast<uint64_t>(t - p.tile0) * kCmTile;
   const uint32_t diag = d < static_cast<uint64_t>(na) + nb ? static_cast<uint32_t>(d) : na + nb;
   const CmRec* in = cm_buf(a, pass & 1);
-  a.split[t] = cm_path_split(in + p.a0, na, in + p.b0, nb, diag, a.tab->runs);
+  a.split[t] = cm_path_split<D>(in + p.a0, na, in + p.b0, nb, diag, a.tab->runs);
 }
 
+template <bool D>
 __global__ __launch_bounds__(kCmTileLanes) void cm_merge_kernel(CmDev a, uint32_t pass) {
   __shared__ cm_u32x4 s[2 * kCmTile];
   if (cm_input_flags(a, false)) return;
@@ -233,7 +244,7 @@ __global__ __launch_bounds__(kCmTileLanes) void cm_merge_kernel(CmDev a, uint32_
   CmRec o[kCmLane];
   const uint32_t o0 = threadIdx.x * kCmLane;
   const uint32_t c = o0 < cnt ? (cnt - o0 < kCmLane ? cnt - o0 : kCmLane) : 0;
-  if (c) cm_merge_lane(sr, na, sr + na, nb, o0, c, o, a.tab->runs);
+  if (c) cm_merge_lane<D>(sr, na, sr + na, nb, o0, c, o, a.tab->runs);
   __syncthreads();
 #pragma unroll
   for (uint32_t k = 0; k < kCmLane; k++)
@@ -252,9 +263,10 @@ __device__ __forceinline__ CmScratch cm_scratch(const CmDev& a) {
   return {p, p + a.n, p + 2 * a.n, p + 3 * a.n};
 }
 
+template <bool D>
 __global__ __launch_bounds__(kCmBlock) void cm_decide_kernel(CmDev a) {
   __shared__ uint64_t sh[kCmWaves];
-  if (cm_input_flags(a, a.n_passes == 0)) return;
+  if (cm_input_flags<D>(a, a.n_passes == 0)) return;
   const CmRun* runs = a.tab->runs;
   const CmRec* rec = cm_buf(a, a.n_passes & 1);
   const CmScratch w = cm_scratch(a);
@@ -264,9 +276,17 @@ __global__ __launch_bounds__(kCmBlock) void cm_decide_kernel(CmDev a) {
     const uint64_t i = c * kCmChunk + threadIdx.x;
     if (i >= a.n) break;
     const CmRec cur = rec[i];
-    const bool drop = a.policy != 0 && i > 0 && cm_hidden(rec[i - 1], cur, a.snapshot, runs);
+    const bool drop = a.policy != 0 && i > 0 && cm_hidden<D>(rec[i - 1], cur, a.snapshot, runs);
     const CmRun& r = runs[cm_run(cur)];
-    const uint64_t ks = drop ? 0 : r.key_size(cm_index(cur)), vs = drop ? 0 : r.value_size(cm_index(cur));
+    uint64_t ks = 0, vs = 0;
+    if (D) {  // one load for both lengths
+      const CmDesc d = drop ? CmDesc{0, 0, 0} : r.desc[cm_index(cur)];
+      ks = d.key_size;
+      vs = d.value_size;
+    } else {
+      ks = drop ? 0 : r.key_size(cm_index(cur));
+      vs = drop ? 0 : r.value_size(cm_index(cur));
+    }
     w.klen[i] = ks;
     w.vlen[i] = vs;
     cnt += drop ? 0 : 1;
@@ -283,6 +303,7 @@ __global__ __launch_bounds__(kCmBlock) void cm_decide_kernel(CmDev a) {
   }
 }
 
+template <bool D>
 __global__ __launch_bounds__(kCmBlock) void cm_offsets_kernel(CmDev a) {
   __shared__ uint64_t sh[kCmWaves];
   __shared__ uint64_t sh3[3][kCmWaves + 1];
@@ -350,8 +371,14 @@ __global__ __launch_bounds__(kCmBlock) void cm_offsets_kernel(CmDev a) {
       const CmRun& r = runs[cm_run(cur)];
       a.wko[j] = ko;
       a.wvo[j] = vo;
-      w.ksrc[j] = r.key_src(cm_index(cur));
-      w.vsrc[j] = r.value_src(cm_index(cur));
+      if (D) {  // the key lies behind the pair's header, the value behind the key
+        const CmDesc d = r.desc[cm_index(cur)];
+        w.ksrc[j] = d.addr + 8;
+        w.vsrc[j] = d.addr + 8 + d.key_size;
+      } else {
+        w.ksrc[j] = r.key_src(cm_index(cur));
+        w.vsrc[j] = r.value_src(cm_index(cur));
+      }
       if (j <= a.pair_cap) {
         a.key_off[j] = ko;
         a.value_off[j] = vo;
@@ -414,33 +441,43 @@ __global__ __launch_bounds__(kCmBlock) void cm_gather_kernel(CmDev a) {
   cm_gather_stream(a.wvo, w.vsrc, m, vb < a.values_cap ? vb : a.values_cap, a.values, soff, ssrc);
 }
 
-}  // namespace
-
-hipError_t launch_compaction_merge(const CmDev& a, const uint32_t* tiles, hipEvent_t* ev, hipStream_t s) {
-  if (a.nwg == 0 || a.nwg > kSortMaxWgs || a.cpw == 0 || a.copy_wgs == 0 || a.n_runs == 0 || a.n_runs > kCmMaxRuns ||
-      a.n_passes > kCmMaxPasses)
-    return hipErrorInvalidValue;
+template <bool D>
+hipError_t cm_launch(const CmDev& a, const uint32_t* tiles, hipEvent_t* ev, hipStream_t s, const TsDev* ts) {
   hipError_t e;
   int marks = 0;
   auto mark = [&]() { return ev ? hipEventRecord(ev[marks++], s) : hipSuccess; };
   if ((e = mark()) != hipSuccess) return e;
-  cm_record_kernel<<<a.nwg, kCmBlock, 0, s>>>(a);
+  if (D) {
+    if ((e = launch_table_record(a, *ts, s)) != hipSuccess) return e;
+  } else {
+    cm_record_kernel<<<a.nwg, kCmBlock, 0, s>>>(a);
+  }
   if ((e = hipGetLastError()) != hipSuccess || (e = mark()) != hipSuccess) return e;
   for (uint32_t p = 0; p < a.n_passes; p++) {
     // (a pass without a tile still launches: the launch count depends on n_runs alone)
     const uint32_t nt = tiles[p] ? tiles[p] : 1;
-    cm_partition_kernel<<<(nt + kCmTileLanes - 1) / kCmTileLanes, kCmTileLanes, 0, s>>>(a, p, tiles[p]);
+    cm_partition_kernel<D><<<(nt + kCmTileLanes - 1) / kCmTileLanes, kCmTileLanes, 0, s>>>(a, p, tiles[p]);
     if ((e = hipGetLastError()) != hipSuccess || (e = mark()) != hipSuccess) return e;
-    cm_merge_kernel<<<nt, kCmTileLanes, 0, s>>>(a, p);
+    cm_merge_kernel<D><<<nt, kCmTileLanes, 0, s>>>(a, p);
     if ((e = hipGetLastError()) != hipSuccess || (e = mark()) != hipSuccess) return e;
   }
-  cm_decide_kernel<<<a.nwg, kCmBlock, 0, s>>>(a);
+  cm_decide_kernel<D><<<a.nwg, kCmBlock, 0, s>>>(a);
   if ((e = hipGetLastError()) != hipSuccess || (e = mark()) != hipSuccess) return e;
-  cm_offsets_kernel<<<a.nwg, kCmBlock, 0, s>>>(a);
+  cm_offsets_kernel<D><<<a.nwg, kCmBlock, 0, s>>>(a);
   if ((e = hipGetLastError()) != hipSuccess || (e = mark()) != hipSuccess) return e;
   cm_gather_kernel<<<a.copy_wgs, kCmBlock, 0, s>>>(a);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   return mark();
+}
+
+}  // namespace
+
+hipError_t launch_compaction_merge(const CmDev& a, const uint32_t* tiles, hipEvent_t* ev, hipStream_t s,
+                                   const TsDev* ts) {
+  if (a.nwg == 0 || a.nwg > kSortMaxWgs || a.cpw == 0 || a.copy_wgs == 0 || a.n_runs == 0 || a.n_runs > kCmMaxRuns ||
+      a.n_passes > kCmMaxPasses)
+    return hipErrorInvalidValue;
+  return ts ? cm_launch<true>(a, tiles, ev, s, ts) : cm_launch<false>(a, tiles, ev, s, nullptr);
 }
 
 }  // namespace dlsm

@@ -1144,5 +1144,53 @@ inline int plan_compaction_merge(const uint64_t* run_n, int n_runs, uint32_t max
   return DLSM_OK;
 }
 
+// ---- compaction merge out of opened tables (table_scan.hip) --------------------
+// dlsm_compaction_merge_tables_dev from the files' entry counts and the runs'
+// file lists alone: the argument rules, the listed files' bases and runs
+// (TsTable) -- run r's inputs are its files' entries in the order listed -- and
+// plan_compaction_merge over the runs' totals, with the table and a 16-byte
+// descriptor per input behind its workspace.  file_n[f]: file f's entries;
+// held[f]: non-zero where its index and its data are held.  tab.runs is left
+// to the caller.
+struct CompactionTablesPlan : CompactionMergePlan {
+  TsTable ts;
+  uint64_t ts_off = 0, ts_bytes = 0;      // TsTable
+  uint64_t desc_off = 0, desc_bytes = 0;  // CmDesc[n]
+};
+
+inline int plan_compaction_tables(const uint32_t* file_n, const uint8_t* held, uint32_t n_files,
+                                  const dlsm_table_run* runs, int n_runs, uint32_t max_wgs, CompactionTablesPlan& P) {
+  if (!runs || n_runs < 1 || n_runs > static_cast<int>(kCmMaxRuns) || (n_files && (!file_n || !held))) return DLSM_E_ARG;
+  TsTable& S = P.ts;
+  S = TsTable();
+  uint64_t run_n[kCmMaxRuns], n = 0;
+  uint32_t k = 0;
+  for (int r = 0; r < n_runs; r++) {
+    if (runs[r].n_files && !runs[r].files) return DLSM_E_ARG;
+    if (runs[r].n_files > kTsMaxFiles - k) return DLSM_E_ARG;
+    run_n[r] = 0;
+    for (uint32_t j = 0; j < runs[r].n_files; j++, k++) {
+      const uint32_t f = runs[r].files[j];
+      if (f >= n_files || !held[f]) return DLSM_E_ARG;
+      S.ebase[k] = n;
+      S.file[k] = f;
+      S.run[k] = static_cast<uint8_t>(r);
+      n += file_n[f];
+      run_n[r] += file_n[f];
+    }
+  }
+  S.n_listed = k;
+  for (; k <= kTsMaxFiles; k++) S.ebase[k] = n;
+  if (n > 0xffffffffull) return DLSM_E_ARG;
+  const int st = plan_compaction_merge(run_n, n_runs, max_wgs, P);
+  if (st != DLSM_OK) return st;
+  Layout ws;
+  ws.at = P.bytes;
+  ws.region(&P.ts_off, &P.ts_bytes, sizeof(TsTable));
+  ws.region(&P.desc_off, &P.desc_bytes, sizeof(CmDesc) * P.n);
+  P.bytes = ws.at;
+  return DLSM_OK;
+}
+
 }  // namespace plan
 }  // namespace dlsm

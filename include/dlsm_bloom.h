@@ -993,12 +993,68 @@ int dlsm_compaction_merge(dlsm_ctx* ctx, const dlsm_merge_run* runs, int n_runs,
 uint32_t dlsm_merge_tile(void);
 uint32_t dlsm_merge_span(void);
 uint32_t dlsm_merge_chunk(void);
-/* The last dlsm_compaction_merge_dev of the context, once its work has
- * completed: launch_ms[6] (or NULL) gets the device time per launch kind --
+/* The last dlsm_compaction_merge_dev or dlsm_compaction_merge_tables_dev of
+ * the context, once its work has completed: launch_ms[6] (or NULL) gets the device time per launch kind --
  * record, partition (all passes), merge (all passes), decide, offsets, gather
  * -- from events recorded around the launches; *passes (or NULL) the number
  * of merge passes. */
 int dlsm_compaction_merge_stats(const dlsm_ctx* ctx, double* launch_ms, uint32_t* passes);
+
+/* The same merge with its inputs read straight out of opened tables: what a
+ * compaction's input iterator yields.  A run is what MakeInputIterator
+ * (db/version_set.cc:1565-1596) makes one child of the merging iterator: one
+ * level-0 file, or the files of a deeper level in key order (4 level-0 files
+ * into 10 files of level 1 are 5 runs, not 14).  Run r's pairs are the entries
+ * of its files in the order listed, concatenated.  Entry i of a file's index
+ * block names pair i by its BlockHandle {offset, size}: the pair's key is the
+ * key_size bytes at offset + 8 in the file's chunks, its value the value_size
+ * bytes behind the key (dlsm_kv_pair_read's layout and locate rules).
+ * Order, rule (A), the caps, merged, key_off, value_off, keys, values and src
+ * are dlsm_compaction_merge_dev's; src[j] = run << 32 | index, the index
+ * counted through the run's concatenated files; merged.n_in is the listed
+ * files' entry total.
+ * DLSM_MERGE_TABLE_MISMATCH is set when, for some entry, the handle names no
+ * `size` bytes of one chunk, the pair's Fixed32 key_size is not the entry's key
+ * length, 8 + key_size + value_size != size, the pair's key bytes differ from
+ * the entry's key, or the entry's offset is not its predecessor's offset + size
+ * (0 for a file's first entry) -- the last rule makes the handles name the very
+ * pairs the reference's sequential walk (ByteAddressableSEQIterator,
+ * table/byte_addressable_SEQ_iterrator.cpp:48-184) visits.
+ * DLSM_MERGE_UNSORTED: two neighbouring pairs of one run do not strictly
+ * ascend; inside a file the open has ruled that out, across a file boundary it
+ * is what overlapping files of one level look like.  With either bit only
+ * `merged` is written, of it only n_in and flags are specified, and no pair is
+ * walked further.  No byte outside the index contents and the chunks is ever
+ * read, flag or not.
+ * DLSM_E_ARG, before any launch: n_runs outside 1..64; the file counts of ti
+ * and td differ; a listed file is >= n_files or has no index or no data held;
+ * more than 1,023 files listed in all; more than UINT32_MAX entries in all.  A
+ * run with no files and a file with no entries are valid.
+ * DLSM_OPT_FAULT_INJECT makes the calls return the injected error.
+ * dlsm_compaction_merge_tables_dev: out device memory (runs[], the file lists
+ * and *out itself host memory); asynchronous on the context's stream, the
+ * launches of dlsm_compaction_merge_dev with a table record pass as the first,
+ * no host read-back, no counter shared between workgroups, no result that
+ * depends on the order of atomics; dlsm_compaction_merge_stats reports it.
+ * dlsm_compaction_merge_tables: the sealed index blocks and chunks in host
+ * memory, in the arguments' form of dlsm_tableindex_create_blocks and
+ * dlsm_tabledata_create; the same rules run on the host (no device is touched;
+ * ctx may be NULL), synchronous.  A listed block that would not open returns
+ * DLSM_E_CORRUPT. */
+typedef struct {          /* one sorted run: files of one level in key order, or one level-0 file */
+  const uint32_t* files;  /* host memory; the numbering of the tableindex / tabledata */
+  uint32_t n_files;
+} dlsm_table_run;
+
+#define DLSM_MERGE_TABLE_MISMATCH 32u
+
+int dlsm_compaction_merge_tables_dev(dlsm_ctx* ctx, const dlsm_tableindex* ti, const dlsm_tabledata* td,
+                                     const dlsm_table_run* runs, int n_runs, int policy,
+                                     uint64_t smallest_snapshot, const dlsm_merge_output* out);
+int dlsm_compaction_merge_tables(dlsm_ctx* ctx, const uint8_t* const* blocks, const uint64_t* lens,
+                                 const dlsm_data_chunk* chunks, const uint32_t* chunk_begin, int n_files,
+                                 const dlsm_table_run* runs, int n_runs, int policy,
+                                 uint64_t smallest_snapshot, const dlsm_merge_output* out);
 
 /* ---- legacy FilterPolicy format (util/bloom.cc) ------------------------- */
 
