@@ -37,6 +37,7 @@ __all__ = [
     "table_build", "table_build_chunk", "table_build_span", "table_build_bound",
     "compaction_merge", "merge_tile", "merge_span", "merge_chunk", "MERGE_KEEP_ALL", "MERGE_DROP_HIDDEN",
     "compaction_merge_tables", "MERGE_TABLE_MISMATCH",
+    "compaction_output", "compaction_output_bound", "output_tables", "OUTPUT_FILE_FIELDS", "OUTPUT_MAX_FILES", "OUTPUT_FILE_CAP", "OUTPUT_INPUT_FLAGGED",
 ]
 
 PATH_AUTO, PATH_DIRECT, PATH_SLICED = 0, 1, 2
@@ -304,6 +305,83 @@ def compaction_merge(runs, policy: int = MERGE_DROP_HIDDEN, smallest_snapshot: i
     m = tuple(int(x) for x in merged)
     p = min(m[1], pair_cap)
     return (keys[:min(m[2], keys_cap)], key_off[:p + 1], values[:min(m[3], values_cap)], value_off[:p + 1], src[:p], m)
+
+
+OUTPUT_MAX_FILES, OUTPUT_FILE_CAP, OUTPUT_INPUT_FLAGGED = 4096, 128, 256  # the other bits are the TABLE_* ones
+OUTPUT_FILE_FIELDS = ("first", "n", "data_base", "data_bytes", "index_base", "index_bytes", "chunk_base", "n_chunks",
+                      "flags")  # a dlsm_output_file: nine uint64
+
+
+def compaction_output_bound(pair_cap: int, key_bytes: int, value_bytes: int, max_file_bytes: int, chunk_bytes: int):
+    """(data_cap, index_cap, chunk_cap, file_cap) that no output of such a run passes."""
+    v = [C.c_uint64() for _ in range(4)]
+    check(lib().dlsm_compaction_output_bound(pair_cap, key_bytes, value_bytes, max_file_bytes, chunk_bytes,
+                                             *[C.byref(x) for x in v]), "compaction_output_bound")
+    return tuple(int(x.value) for x in v)
+
+
+def _output_io(keys: "Keys", values, value_off, value_len: int, merged, max_file_bytes: int, chunk_bytes: int, data,
+               data_cap, index, index_cap, chunk_end, chunk_cap, files, file_cap, built):
+    n = keys.n
+    if value_off is not None:
+        _need(value_off, 8 * (n + 1), "value_off")
+    else:
+        _need(values, n * value_len, "values")
+    data_cap = _nbytes(data) if data_cap is None else int(data_cap)
+    index_cap = _nbytes(index) if index_cap is None else int(index_cap)
+    chunk_cap = _nbytes(chunk_end) // 8 if chunk_cap is None else int(chunk_cap)
+    file_cap = _nbytes(files) // 72 if file_cap is None else int(file_cap)
+    for x, nb, what in ((data, data_cap, "data"), (index, index_cap, "index"), (chunk_end, 8 * chunk_cap, "chunk_end"),
+                        (files, 72 * file_cap, "files"), (built, 40, "built"), (merged, 40, "merged")):
+        _need(x, nb, what)
+    oi = _L.dlsm_output_input(keys.c(), _ptr(values), _ptr(value_off), value_len, _ptr(merged), max_file_bytes,
+                              chunk_bytes)
+    oo = _L.dlsm_output_output(_ptr(data), data_cap, _ptr(index), index_cap, _ptr(chunk_end), chunk_cap, _ptr(files),
+                               file_cap, _ptr(built))
+    return oi, oo
+
+
+def compaction_output(keys: "Keys", values: np.ndarray, merged, *, value_off: Optional[np.ndarray] = None,
+                      value_len: int = 0, max_file_bytes: int = 0, chunk_bytes: int = 0, data_cap: Optional[int] = None,
+                      index_cap: Optional[int] = None, chunk_cap: Optional[int] = None, file_cap: Optional[int] = None,
+                      ctx: Optional["Context"] = None):
+    """The host form of the compaction output (dlsm_compaction_output; no
+    device is touched): the run a compaction merge returned -- ``keys`` with
+    keys.n the pair capacity, ``values``, ``merged`` (its five-number record, of
+    which n_out pairs are taken) -- cut at ``max_file_bytes`` and built file by
+    file.  Returns (tables, files, built): per file below the caps (data uint8,
+    chunk_end uint64, index_block uint8), the file records (uint64[F, 9],
+    OUTPUT_FILE_FIELDS) and built = (n_files, data_bytes, index_bytes, n_chunks,
+    flags).  The caps default to dlsm_compaction_output_bound's."""
+    n = keys.n
+    kb = int(keys.offsets[n] - keys.offsets[0]) if keys.offsets is not None else n * keys.key_len
+    vb = int(value_off[n] - value_off[0]) if value_off is not None else n * value_len
+    need = compaction_output_bound(n, kb, vb, max_file_bytes, chunk_bytes)
+    need = need[:3] + (min(need[3], OUTPUT_MAX_FILES),)
+    data_cap, index_cap, chunk_cap, file_cap = (b if c is None else int(c) for b, c in
+                                                zip(need, (data_cap, index_cap, chunk_cap, file_cap)))
+    data, index = np.zeros(max(data_cap, 1), dtype=np.uint8), np.zeros(max(index_cap, 1), dtype=np.uint8)
+    ends, files = np.zeros(max(chunk_cap, 1), dtype=np.uint64), np.zeros((max(file_cap, 1), 9), dtype=np.uint64)
+    built, m = np.zeros(5, dtype=np.uint64), np.ascontiguousarray(merged, dtype=np.uint64)
+    oi, oo = _output_io(keys, values, value_off, value_len, m, max_file_bytes, chunk_bytes, data, data_cap, index,
+                        index_cap, ends, chunk_cap, files, file_cap, built)
+    check(lib().dlsm_compaction_output(ctx.h if ctx is not None else None, C.byref(oi), C.byref(oo)),
+          "compaction_output")
+    b = tuple(int(x) for x in built)
+    files = files[:min(b[0], file_cap)]
+    return output_tables(data[:data_cap], index[:index_cap], ends[:chunk_cap], files), files, b
+
+
+def output_tables(data, index, chunk_end, files):
+    """Slice a compaction output's buffers by its file records: (data,
+    chunk_end, index_block) per file, each cut at its buffer's end."""
+    out = []
+    for r in files:
+        r = {k: int(v) for k, v in zip(OUTPUT_FILE_FIELDS, r)}
+        out.append((data[r["data_base"]:r["data_base"] + r["data_bytes"]],
+                    chunk_end[r["chunk_base"]:r["chunk_base"] + r["n_chunks"]],
+                    index[r["index_base"]:r["index_base"] + r["index_bytes"]]))
+    return out
 
 
 def kv_pair_read(chunks, handle, user_key: bytes, state: int = GET_FOUND):
@@ -1192,6 +1270,35 @@ class Context:
         mr, mo = _merge_io(runs, keys, keys_cap, key_off, values, values_cap, value_off, src, pair_cap, merged)
         check(lib().dlsm_compaction_merge_dev(self.h, mr, len(runs), policy, smallest_snapshot, C.byref(mo)),
               "compaction_merge_dev")
+
+    # -- compaction output: a merged run cut into size-capped tables ---------------
+    def compaction_output_dev(self, keys: Keys, values, merged, data, index, chunk_end, files, built, *, value_off=None,
+                              value_len: int = 0, max_file_bytes: int = 0, chunk_bytes: int = 0,
+                              data_cap: Optional[int] = None, index_cap: Optional[int] = None,
+                              chunk_cap: Optional[int] = None, file_cap: Optional[int] = None):
+        """Write every output table of a compaction on the device: ``keys``
+        (keys.n the pair capacity), ``values`` / ``value_off`` and ``merged``
+        (device uint64[5], read on the device) are what compaction_merge_dev
+        left.  data / index (device uint8, 16-byte aligned), chunk_end (device
+        uint64), files (device uint64[file_cap * 9], OUTPUT_FILE_FIELDS) and
+        built (device uint64[5]: n_files, data_bytes, index_bytes, n_chunks,
+        flags) are written; the caps default to the buffers' lengths.
+        Asynchronous, no host read-back."""
+        oi, oo = _output_io(keys, values, value_off, value_len, merged, max_file_bytes, chunk_bytes, data, data_cap,
+                            index, index_cap, chunk_end, chunk_cap, files, file_cap, built)
+        check(lib().dlsm_compaction_output_dev(self.h, C.byref(oi), C.byref(oo)), "compaction_output_dev")
+
+    def compaction_output(self, keys: Keys, values, merged, **kw):
+        """The host-memory form (see dlsm_amd.compaction_output)."""
+        return compaction_output(keys, values, merged, ctx=self, **kw)
+
+    def compaction_output_stats(self):
+        """(size, offsets, cut, entries, region, index, seal) device
+        milliseconds of the last compaction_output_dev (call after sync) and
+        the writes' grid in workgroups."""
+        ms, wgs = (C.c_double * 7)(), C.c_uint32()
+        check(lib().dlsm_compaction_output_stats(self.h, ms, C.byref(wgs)), "compaction_output_stats")
+        return tuple(float(x) for x in ms), int(wgs.value)
 
     def compaction_merge(self, runs, policy: int = MERGE_DROP_HIDDEN, smallest_snapshot: int = 0, **kw):
         """The host-memory form (see dlsm_amd.compaction_merge)."""

@@ -72,6 +72,17 @@ class dlsm_table_output(C.Structure):
                 ("chunk_end", C.c_void_p), ("chunk_cap", C.c_uint64), ("built", C.c_void_p)]
 
 
+class dlsm_output_input(C.Structure):
+    _fields_ = [("keys", dlsm_keyset), ("values", C.c_void_p), ("value_off", C.c_void_p), ("value_len", C.c_uint32),
+                ("merged", C.c_void_p), ("max_file_bytes", C.c_uint64), ("chunk_bytes", C.c_uint64)]
+
+
+class dlsm_output_output(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("data_cap", C.c_uint64), ("index", C.c_void_p), ("index_cap", C.c_uint64),
+                ("chunk_end", C.c_void_p), ("chunk_cap", C.c_uint64), ("files", C.c_void_p), ("file_cap", C.c_uint64),
+                ("built", C.c_void_p)]
+
+
 class dlsm_merge_run(C.Structure):
     _fields_ = [("keys", dlsm_keyset), ("values", C.c_void_p), ("value_off", C.c_void_p), ("value_len", C.c_uint32)]
 
@@ -223,6 +234,11 @@ SIGNATURES = [
     ("dlsm_table_build_chunk", C.c_uint32, []),
     ("dlsm_table_build_span", C.c_uint32, []),
     ("dlsm_table_build_stats", C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
+    ("dlsm_compaction_output_dev", C.c_int, [_VP, C.POINTER(dlsm_output_input), C.POINTER(dlsm_output_output)]),
+    ("dlsm_compaction_output", C.c_int, [_VP, C.POINTER(dlsm_output_input), C.POINTER(dlsm_output_output)]),
+    ("dlsm_compaction_output_bound", C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _U64P, _U64P,
+                                               _U64P, _U64P]),
+    ("dlsm_compaction_output_stats", C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
     ("dlsm_compaction_merge_dev", C.c_int, [_VP, C.POINTER(dlsm_merge_run), C.c_int, C.c_int, C.c_uint64,
                                             C.POINTER(dlsm_merge_output)]),
     ("dlsm_compaction_merge", C.c_int, [_VP, C.POINTER(dlsm_merge_run), C.c_int, C.c_int, C.c_uint64,

@@ -1,4 +1,4 @@
-"""The compaction merge in pure Python (never calls the library).
+"""The compaction merge in pure Python (only open_output calls the library).
 
 ``MergingIterator`` (table/merger.cc:178-199) over the compaction's inputs
 yields every pair in ``InternalKeyComparator::Compare`` order
@@ -78,3 +78,19 @@ def merge_runs(runs, policy=DROP_HIDDEN, snapshot=0):
             pairs.append((ik, value))
             src.append(r << 32 | i)
     return pairs, src
+
+
+def open_output(ctx, data, index, chunk_end, files):
+    """Open what ``Context.compaction_output_dev`` wrote where it lies: ``data``
+    and ``index`` are the call's device tensors, ``chunk_end`` and ``files``
+    host copies of its chunk ends and file records (one read each).  Returns a
+    (TableIndex, TableData) pair over the files, file f of the call being file
+    f of both."""
+    import dlsm_amd
+
+    blocks, chunks = [], []
+    for d, ends, blk in dlsm_amd.output_tables(data, index, chunk_end, files):
+        blocks.append(blk)
+        begin = [0] + [int(e) for e in ends[:-1]]
+        chunks.append([d[b:int(e)] for b, e in zip(begin, ends)])
+    return dlsm_amd.TableIndex(ctx, blocks, on_device=True), dlsm_amd.TableData(ctx, chunks, on_device=True)

@@ -166,6 +166,9 @@ struct dlsm_ctx {
   const uint8_t* tb_seal_index = nullptr;  // table build: the block whose seal descriptor lies in tb_ws ...
   uint64_t tb_seal_cap = 0, tb_seal_gen = 0;  // ... its capacity, and tb_ws's generation then
   hipStream_t tb_seal_stream = nullptr;       // ... and the stream the descriptor went up on
+  DevBuf<uint8_t> co_ws;     // compaction output: offsets, entry starts, per-file tables (plan::CompactionOutputPlan's layout)
+  hipEvent_t ev_co[8] = {};  // compaction output: around its launches (dlsm_compaction_output_stats)
+  bool co_timed = false;     // the last dlsm_compaction_output_dev recorded all eight
   DevBuf<uint8_t> cm_ws;      // compaction merge: table, records, offsets, partial sums (plan::CompactionMergePlan's layout)
   hipEvent_t ev_cm[2 * kCmMaxPasses + 5] = {};  // compaction merge: around every launch (dlsm_compaction_merge_stats)
   uint32_t cm_passes = 0;     // ... the last call's merge passes
@@ -601,6 +604,7 @@ int dlsm_ctx_destroy(dlsm_ctx* ctx) {
   ctx->kv_ws.release();
   ctx->tb_ws.release();
   ctx->cm_ws.release();
+  ctx->co_ws.release();
   ctx->sel.release();
   ctx->st_keys.release();
   ctx->st_offs.release();
@@ -620,6 +624,8 @@ int dlsm_ctx_destroy(dlsm_ctx* ctx) {
   for (hipEvent_t e : ctx->ev_kv)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->ev_tb)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : ctx->ev_co)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->ev_cm)
     if (e) (void)hipEventDestroy(e);
@@ -832,7 +838,7 @@ int dlsm_ctx_stats(dlsm_ctx* ctx, uint64_t* device_allocs, uint64_t* device_byte
   add(ctx->vgl); add(ctx->vabyte); add(ctx->vplan); add(ctx->plan_ws); add(ctx->route_ws);
   add(ctx->st_keys); add(ctx->st_offs); add(ctx->st_out); add(ctx->st_len); add(ctx->st_filter);
   add(ctx->crc_streams); add(ctx->crc_partial); add(ctx->crc_tabs); add(ctx->crc_outp); add(ctx->crc_cap);
-  add(ctx->crc_val); add(ctx->sel); add(ctx->kv_ws); add(ctx->tb_ws); add(ctx->cm_ws);
+  add(ctx->crc_val); add(ctx->sel); add(ctx->kv_ws); add(ctx->tb_ws); add(ctx->cm_ws); add(ctx->co_ws);
   if (device_allocs) *device_allocs = n;
   if (device_bytes) *device_bytes = b;
   return DLSM_OK;
@@ -3270,6 +3276,182 @@ int dlsm_table_build(dlsm_ctx* ctx, const dlsm_table_input* in, const dlsm_table
     const uint32_t m = dlsm_crc32c_mask(dlsm_crc32c_extend(0, out->index, ctot + 1));
     memcpy(out->index + ctot + 1, &m, 4);
   }
+  return DLSM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Compaction output: a merged run cut into size-capped tables, each built as
+// dlsm_table_build builds it (DoCompactionWork, db/db_impl.cc:3562-3573;
+// compaction_output.hip)
+// ---------------------------------------------------------------------------
+int dlsm_compaction_output_bound(uint64_t pair_cap, uint64_t key_bytes, uint64_t value_bytes, uint64_t max_file_bytes,
+                                 uint64_t chunk_bytes, uint64_t* data_cap, uint64_t* index_cap, uint64_t* chunk_cap,
+                                 uint64_t* file_cap) {
+  return plan_compaction_output_bound(pair_cap, key_bytes, value_bytes, max_file_bytes, chunk_bytes, data_cap, index_cap,
+                                      chunk_cap, file_cap);
+}
+
+static int compaction_output_args(const dlsm_output_input* in, const dlsm_output_output* out) {
+  if (!in || !out || !out->built || !in->merged || in->keys.n > 0xffffffffull || out->file_cap > kCoMaxFiles)
+    return DLSM_E_ARG;
+  DLSM_CHECK(validate_keyset(in->keys));
+  if ((out->data_cap && !out->data) || (out->index_cap && !out->index) || (out->chunk_cap && !out->chunk_end) ||
+      (out->file_cap && !out->files))
+    return DLSM_E_ARG;
+  if (in->keys.n && !in->values && (in->value_off || in->value_len)) return DLSM_E_ARG;
+  return DLSM_OK;
+}
+
+int dlsm_compaction_output_dev(dlsm_ctx* ctx, const dlsm_output_input* in, const dlsm_output_output* out) {
+  if (!ctx) return DLSM_E_ARG;
+  DLSM_CHECK(compaction_output_args(in, out));
+  if (!aligned(out->data, 16) || !aligned(out->index, 16) || !aligned(out->chunk_end, 8) || !aligned(out->built, 8) ||
+      !aligned(out->files, 8) || !aligned(in->merged, 8) || !aligned(in->keys.offsets, 8) || !aligned(in->value_off, 8))
+    return DLSM_E_ARG;
+  CompactionOutputPlan P;
+  DLSM_CHECK(plan_compaction_output(in->keys.n, out->index_cap, out->file_cap, kSortMaxWgs, P));
+  if (ctx->fault) return -ctx->fault;
+  DeviceGuard g(ctx->device);
+  if (!ctx->cus) {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || cus <= 0)
+      cus = kTbWgs / kTbWgsPerCu;
+    ctx->cus = cus;
+  }
+  const uint32_t wgs = plan_table_build_wgs(static_cast<uint32_t>(ctx->cus));
+  for (hipEvent_t& e : ctx->ev_co)
+    if (!e) DLSM_TRY(hipEventCreate(&e));
+  ctx->co_timed = false;
+  DLSM_CHECK(ctx->co_ws.ensure(P.bytes));
+  uint8_t* ws = ctx->co_ws.p;
+  CoDev a{};
+  a.off = reinterpret_cast<uint64_t*>(ws + P.off_off);
+  dlsm_table_input ti{in->keys, in->values, in->value_off, in->value_len, in->chunk_bytes};
+  a.src = table_build_source(ti, a.off);
+  a.merged = reinterpret_cast<const uint64_t*>(in->merged);
+  a.pair_cap = in->keys.n;
+  a.max_file_bytes = in->max_file_bytes;
+  a.chunk_bytes = in->chunk_bytes;
+  a.data = out->data;
+  a.data_cap = out->data_cap;
+  a.index = out->index;
+  a.index_cap = out->index_cap;
+  a.chunk_end = out->chunk_end;
+  a.chunk_cap = out->chunk_cap;
+  a.files = reinterpret_cast<CoFile*>(out->files);
+  a.file_cap = out->file_cap;
+  a.built = reinterpret_cast<uint64_t*>(out->built);
+  a.erel = reinterpret_cast<uint64_t*>(ws + P.erel_off);
+  a.es = reinterpret_cast<uint32_t*>(ws + P.es_off);
+  a.wg_sum = reinterpret_cast<uint64_t*>(ws + P.sum_off);
+  a.wg_esum = reinterpret_cast<uint64_t*>(ws + P.esum_off);
+  a.wg_flags = reinterpret_cast<uint64_t*>(ws + P.flag_off);
+  a.tot = reinterpret_cast<uint64_t*>(ws + P.tot_off);
+  a.cut = reinterpret_cast<uint32_t*>(ws + P.cut_off);
+  a.data_base = reinterpret_cast<uint64_t*>(ws + P.dbase_off);
+  a.rspan = reinterpret_cast<uint32_t*>(ws + P.rspan_off);
+  a.nch = reinterpret_cast<uint32_t*>(ws + P.nch_off);
+  a.fflag = reinterpret_cast<uint32_t*>(ws + P.fflag_off);
+  a.fE = reinterpret_cast<uint64_t*>(ws + P.fE_off);
+  a.index_base = reinterpret_cast<uint64_t*>(ws + P.ibase_off);
+  a.ispan = reinterpret_cast<uint32_t*>(ws + P.ispan_off);
+  a.part0 = reinterpret_cast<uint32_t*>(ws + P.part0_off);
+  a.seal_len = reinterpret_cast<uint64_t*>(ws + P.seal_off);
+  a.partial = reinterpret_cast<uint32_t*>(ws + P.partial_off);
+  a.cpw = P.cpw;
+  a.nwg = P.nwg;
+  a.copy_wgs = wgs;
+  DLSM_TRY(launch_compaction_output(a, wgs, P.seal_wgs, ctx->ev_co, ctx->stream));
+  ctx->co_timed = true;
+  return DLSM_OK;
+}
+static_assert(sizeof(dlsm_output_file) == sizeof(CoFile), "the file record is the kernels' CoFile");
+
+int dlsm_compaction_output_stats(const dlsm_ctx* ctx, double* launch_ms, uint32_t* write_wgs) {
+  if (!ctx) return DLSM_E_ARG;
+  if (write_wgs) *write_wgs = ctx->cus ? plan_table_build_wgs(static_cast<uint32_t>(ctx->cus)) : 0;
+  if (launch_ms) {
+    for (int j = 0; j < 7; j++) launch_ms[j] = 0;
+    if (!ctx->co_timed) return DLSM_OK;
+    DeviceGuard g(ctx->device);
+    for (int j = 0; j < 7; j++) {
+      float ms = 0;
+      DLSM_TRY(hipEventElapsedTime(&ms, ctx->ev_co[j], ctx->ev_co[j + 1]));
+      launch_ms[j] = ms;
+    }
+  }
+  return DLSM_OK;
+}
+
+// The host form: the cut rule of compaction_output.h over the run's offsets,
+// then dlsm_table_build on every file's pairs with what is left of the caps
+// behind the file's bases.
+int dlsm_compaction_output(dlsm_ctx* ctx, const dlsm_output_input* in, const dlsm_output_output* out) {
+  DLSM_CHECK(compaction_output_args(in, out));
+  if (ctx && ctx->fault) return -ctx->fault;
+  dlsm_output_built B{};
+  if (in->merged->flags != 0 || in->merged->n_out > in->keys.n) {
+    B.flags = kCoInputFlagged;
+    *out->built = B;
+    return DLSM_OK;
+  }
+  const uint64_t n = in->merged->n_out;
+  std::vector<uint64_t> off(n + 1);
+  dlsm_table_input whole{in->keys, in->values, in->value_off, in->value_len, in->chunk_bytes};
+  const TbSource src = table_build_source(whole, off.data());
+  uint64_t bad = 0;
+  for (uint64_t i = 0; i < n; i++) {
+    const uint64_t ks = src.key_size(i), vs = src.value_size(i), p = tb_pair_size(ks, vs);
+    if (ks < 8) bad |= kTbShortKey;
+    if (ks > 0xffffffffull || vs > 0xffffffffull || p > 0xffffffffull) bad |= kTbPairTooBig;
+    off[i + 1] = off[i] + p;
+  }
+  uint64_t files = 0, chunks = 0;
+  for (uint64_t at = 0; at < n && !bad; files++) {
+    const uint64_t next = co_cut_next(off.data(), n, at, in->max_file_bytes);
+    if (files >= kCoMaxFiles) {  // counted and sized, not built
+      B.data_bytes += co_pad16(off[next] - off[at]);
+      at = next;
+      continue;
+    }
+    dlsm_table_input ti = whole;
+    ti.keys.n = next - at;
+    if (ti.keys.offsets) ti.keys.offsets += at;
+    else ti.keys.bytes += at * ti.keys.key_len;
+    if (ti.value_off) ti.value_off += at;
+    else if (ti.values) ti.values += at * ti.value_len;
+    dlsm_table_built tb{};
+    dlsm_table_output to{};
+    to.data_cap = co_left(out->data_cap, B.data_bytes);
+    to.data = to.data_cap ? out->data + B.data_bytes : nullptr;
+    to.index_cap = co_left(out->index_cap, B.index_bytes);
+    to.index = to.index_cap ? out->index + B.index_bytes : nullptr;
+    to.chunk_cap = co_left(out->chunk_cap, chunks);
+    to.chunk_end = to.chunk_cap ? out->chunk_end + chunks : nullptr;
+    to.built = &tb;
+    DLSM_CHECK(dlsm_table_build(nullptr, &ti, &to));
+    bad |= tb.flags & kTbMalformed;
+    if (bad) break;
+    if (files < out->file_cap)
+      out->files[files] = dlsm_output_file{at,        next - at,      B.data_bytes, tb.data_bytes,           B.index_bytes,
+                                           tb.index_bytes, chunks, tb.n_chunks,  tb.flags & kTbOversizePair};
+    B.flags |= tb.flags & kTbOversizePair;
+    B.data_bytes += co_pad16(tb.data_bytes);
+    B.index_bytes += co_pad16(tb.index_bytes);
+    chunks += tb.n_chunks;
+    at = next;
+  }
+  if (bad) {
+    B = dlsm_output_built{};
+    B.flags = bad;
+    *out->built = B;
+    return DLSM_OK;
+  }
+  B.n_files = files;
+  B.n_chunks = chunks;
+  B.flags |= (B.data_bytes > out->data_cap ? kTbDataCap : 0) | (B.index_bytes > out->index_cap ? kTbIndexCap : 0) |
+             (chunks > out->chunk_cap ? kTbChunkCap : 0) | (files > out->file_cap || files > kCoMaxFiles ? kCoFileCap : 0);
+  *out->built = B;
   return DLSM_OK;
 }
 

@@ -12,6 +12,7 @@
 #include "read_plan.h"
 #include "shard_route.h"
 #include "table_build.h"
+#include "compaction_output.h"
 #include "table_scan.h"
 
 namespace dlsm {
@@ -548,6 +549,48 @@ struct TbDev {
 };
 // ev: five events recorded around the four launches, or nullptr.
 hipError_t launch_table_build(const TbDev& a, uint32_t index_wgs, hipEvent_t* ev, hipStream_t s);
+
+// compaction_output.hip: a merged run cut into size-capped tables, every one
+// built in the same launches (dlsm_compaction_output_dev).  Workspace in
+// plan::CompactionOutputPlan's layout; the per-file tables hold kCoMaxFiles + 1
+// values each.
+struct CoDev {
+  TbSource src;            // the run; src.off = off
+  const uint64_t* merged;  // the merge's dlsm_merged on the device: n_out at [1], flags at [4]
+  uint64_t pair_cap;       // the host's bound on n_out
+  uint64_t max_file_bytes, chunk_bytes;
+  uint8_t* data;           // 16-byte aligned
+  uint64_t data_cap;
+  uint8_t* index;          // 16-byte aligned
+  uint64_t index_cap;
+  uint64_t* chunk_end;
+  uint64_t chunk_cap;
+  CoFile* files;           // dlsm_output_file[file_cap]
+  uint64_t file_cap;
+  uint64_t* built;         // dlsm_output_built: n_files, data_bytes, index_bytes, n_chunks, flags
+  uint64_t* off;           // workspace u64[pair_cap + 1]: the pairs' offsets in the run and the total
+  uint64_t* erel;          // workspace u64[pair_cap]: entry starts relative to the entries pass's workgroup
+  uint32_t* es;            // workspace u32[pair_cap + 2 * kCoMaxFiles]: per file entry starts, pair count, a pad
+  uint64_t* wg_sum;        // workspace u64[nwg]: pair bytes per workgroup
+  uint64_t* wg_esum;       // workspace u64[nwg]: entry bytes per workgroup
+  uint64_t* wg_flags;      // workspace u64[nwg]: malformed-input bits per workgroup
+  uint64_t* tot;           // workspace u64[16]: what the launches hand on (compaction_output.hip)
+  uint32_t* cut;           // workspace, per file: the first pair; [nf]: the end of the pairs that have a file
+  uint64_t* data_base;     // ... the region's place; [nf]: the padded total
+  uint32_t* rspan;         // ... the region write's spans in front of the file
+  uint32_t* nch;           // ... the chunk count
+  uint32_t* fflag;         // ... kTbOversizePair or 0
+  uint64_t* fE;            // ... the entry bytes
+  uint64_t* index_base;    // ... the block's place
+  uint32_t* ispan;         // ... the index write's spans in front of the file
+  uint32_t* part0;         // ... the seal's parts in front of the file
+  uint64_t* seal_len;      // ... the contents' length where the block fits, else 0
+  uint32_t* partial;       // workspace u32[seal_wgs]: the parts' raw crcs
+  uint32_t cpw, nwg;       // plan::sort_grid(pair_cap, kTbChunk, kSortMaxWgs), at least one workgroup
+  uint32_t copy_wgs;       // the region write's persistent grid
+};
+// ev: eight events recorded around the launches (the seal's two as one), or nullptr.
+hipError_t launch_compaction_output(const CoDev& a, uint32_t index_wgs, uint32_t seal_wgs, hipEvent_t* ev, hipStream_t s);
 
 // compaction_merge.hip: R sorted runs into one run in the table build's input
 // form (dlsm_compaction_merge_dev).  Workspace in plan::CompactionMergePlan's

@@ -1075,6 +1075,76 @@ inline int plan_table_build_bound(uint64_t n, uint64_t key_bytes, uint64_t value
   return DLSM_OK;
 }
 
+// ---- compaction output (compaction_output.hip) ---------------------------------
+// dlsm_compaction_output_dev from the host's bound on the pair count: the
+// per-pair grid (one workgroup where there is no pair: it writes the totals),
+// the seal's flat grid -- a block of c content bytes has at most c / 32 KiB + 1
+// parts, so index_cap / 32 KiB + the most files bounds them all -- and the
+// workspace layout (byte offsets, every region 256-byte aligned): 20 bytes per
+// pair plus the per-file tables and the partial sums.
+struct CompactionOutputPlan : SortGrid {
+  uint32_t seal_wgs = 0;
+  uint64_t tot_off = 0, off_off = 0, erel_off = 0, es_off = 0, sum_off = 0, esum_off = 0, flag_off = 0;
+  uint64_t cut_off = 0, dbase_off = 0, rspan_off = 0, nch_off = 0, fflag_off = 0, fE_off = 0, ibase_off = 0,
+           ispan_off = 0, part0_off = 0, seal_off = 0, partial_off = 0;
+  uint64_t bytes = 0;
+};
+
+inline int plan_compaction_output(uint64_t pair_cap, uint64_t index_cap, uint64_t file_cap, uint32_t max_wgs,
+                                  CompactionOutputPlan& P) {
+  if (pair_cap > 0xffffffffull || file_cap > kCoMaxFiles || max_wgs == 0) return DLSM_E_ARG;
+  const uint64_t parts = index_cap / (16ull * kCoSealPieces) + std::min<uint64_t>(pair_cap, kCoMaxFiles) + 1;
+  if (parts > 0x7fffffffull) return DLSM_E_ARG;
+  P = CompactionOutputPlan();
+  static_cast<SortGrid&>(P) = sort_grid(pair_cap, kTbChunk, max_wgs);
+  P.nwg = std::max<uint32_t>(P.nwg, 1);
+  P.seal_wgs = static_cast<uint32_t>(parts);
+  const uint64_t F = kCoMaxFiles + 1;
+  uint64_t unused;
+  Layout ws;
+  ws.region(&P.tot_off, &unused, sizeof(uint64_t) * 16);
+  ws.region(&P.off_off, &unused, sizeof(uint64_t) * (pair_cap + 1));
+  ws.region(&P.erel_off, &unused, sizeof(uint64_t) * pair_cap);
+  ws.region(&P.es_off, &unused, sizeof(uint32_t) * (pair_cap + 2 * uint64_t(kCoMaxFiles)));
+  ws.region(&P.sum_off, &unused, sizeof(uint64_t) * P.nwg);
+  ws.region(&P.esum_off, &unused, sizeof(uint64_t) * P.nwg);
+  ws.region(&P.flag_off, &unused, sizeof(uint64_t) * P.nwg);
+  ws.region(&P.cut_off, &unused, sizeof(uint32_t) * F);
+  ws.region(&P.dbase_off, &unused, sizeof(uint64_t) * F);
+  ws.region(&P.rspan_off, &unused, sizeof(uint32_t) * F);
+  ws.region(&P.nch_off, &unused, sizeof(uint32_t) * F);
+  ws.region(&P.fflag_off, &unused, sizeof(uint32_t) * F);
+  ws.region(&P.fE_off, &unused, sizeof(uint64_t) * F);
+  ws.region(&P.ibase_off, &unused, sizeof(uint64_t) * F);
+  ws.region(&P.ispan_off, &unused, sizeof(uint32_t) * F);
+  ws.region(&P.part0_off, &unused, sizeof(uint32_t) * F);
+  ws.region(&P.seal_off, &unused, sizeof(uint64_t) * F);
+  ws.region(&P.partial_off, &unused, sizeof(uint32_t) * parts);
+  P.bytes = ws.at;
+  return DLSM_OK;
+}
+
+// dlsm_compaction_output_bound: capacities no output of a run of at most
+// pair_cap pairs with key_bytes and value_bytes in all passes.  A file other
+// than the last holds max_file_bytes or more, so there are at most
+// data / max_file_bytes + 1 of them (and never more than pairs); each adds up
+// to 15 pad bytes to the region and to its block, a 9-byte empty block's worth
+// of count and trailer, and one chunk more than the bytes alone need (two
+// neighbouring chunks of a file hold more than chunk_bytes together).
+inline int plan_compaction_output_bound(uint64_t pair_cap, uint64_t key_bytes, uint64_t value_bytes,
+                                        uint64_t max_file_bytes, uint64_t chunk_bytes, uint64_t* data_cap,
+                                        uint64_t* index_cap, uint64_t* chunk_cap, uint64_t* file_cap) {
+  uint64_t d, x;
+  if (plan_table_build_bound(pair_cap, key_bytes, value_bytes, &d, &x) != DLSM_OK) return DLSM_E_ARG;
+  const uint64_t files = max_file_bytes ? std::min(pair_cap, d / max_file_bytes + 1) : std::min<uint64_t>(pair_cap, 1);
+  const uint64_t chunks = chunk_bytes ? std::min(pair_cap, 2 * (d / chunk_bytes) + 1 + files) : files;
+  if (data_cap) *data_cap = d + 15 * files;
+  if (index_cap) *index_cap = x + (15 + 9) * files;
+  if (chunk_cap) *chunk_cap = chunks;
+  if (file_cap) *file_cap = files;
+  return DLSM_OK;
+}
+
 // ---- compaction merge (compaction_merge.hip) -----------------------------------
 // dlsm_compaction_merge_dev from the runs' pair counts alone: the runs' bases,
 // ceil(log2 R) passes of two-way merges -- pass p pairs neighbouring segments

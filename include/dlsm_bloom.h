@@ -1056,6 +1056,116 @@ int dlsm_compaction_merge_tables(dlsm_ctx* ctx, const uint8_t* const* blocks, co
                                  const dlsm_table_run* runs, int n_runs, int policy,
                                  uint64_t smallest_snapshot, const dlsm_merge_output* out);
 
+/* ---- compaction output: a merged run cut into size-capped tables --------- */
+
+/* The last step of a compaction: DBImpl::DoCompactionWork closes its output
+ * file as soon as builder->FileSize() >= MaxOutputFileSize()
+ * (db/db_impl.cc:3562-3573) and opens the next, so one merged run leaves as
+ * several tables, each with offsets, chunk chain and index block of its own.
+ * The call takes the run a compaction merge left on the device -- keys,
+ * key_off, values, value_off and the dlsm_merged record, which is read ON THE
+ * DEVICE for n_out and flags -- and writes every output table.  Each output is
+ * a pure function of the inputs:
+ *   cut: off[i] is the exclusive sum of 8 + key_size + value_size over the run.
+ *   File f starts at pair first[f], first[0] = 0; first[f + 1] is the smallest
+ *   e > first[f] with off[e] - off[first[f]] >= max_file_bytes, or n where there
+ *   is none: the pair that reaches the threshold stays in the file (FileSize()
+ *   is the builder's offset after Add, table_builder_bacs.cpp:226,666), a pair
+ *   larger than the threshold is a file of its own.  max_file_bytes = 0: one
+ *   file.  n = 0: no file (the reference opens no builder when nothing is
+ *   kept).  The threshold is taken as MaxOutputFileSize() gives it; nothing is
+ *   subtracted.  n_files is exact whatever file_cap is;
+ *   per file: for the pairs [first[f], first[f + 1]) the data region, the
+ *   running chunk ends and the sealed index block are byte for byte what
+ *   dlsm_table_build gives for those pairs alone with the same chunk_bytes:
+ *   offsets, the flush rule and the handles restart at the file's first pair;
+ *   placement: file f's region starts at data + data_base[f], its block at
+ *   index + index_base[f]; both bases are exclusive sums of the lengths rounded
+ *   up to 16, so every file meets dlsm_table_output's alignment and opens as it
+ *   lies with dlsm_tableindex_create_blocks / dlsm_tabledata_create
+ *   (chunks_are_device = 1).  The pad bytes are not written.  File f's chunk
+ *   ends go to chunk_end + chunk_base[f], the exclusive sum of the chunk
+ *   counts;
+ *   files[f], for f < min(n_files, file_cap): first, n, the bases and lengths
+ *   above, n_chunks and flags (DLSM_TABLE_OVERSIZE_PAIR or 0).  The file's
+ *   smallest and largest keys are keys first and first + n - 1 of the run;
+ *   built: n_files; data_bytes and index_bytes, the sums of the padded
+ *   lengths; n_chunks; flags.  All exact whatever the four caps are.
+ * flags: DLSM_OUTPUT_DATA_CAP / INDEX_CAP / CHUNK_CAP / FILE_CAP where a total
+ * is larger than its cap (the values of the DLSM_TABLE_* bits, FILE_CAP new).
+ * Every byte below a cap is still the right one, except that a block's 5-byte
+ * trailer is written only when the whole block lies below index_cap; every
+ * file is written whatever file_cap is, only the records stop there.  Nothing
+ * is ever written at or past a cap.  DLSM_TABLE_OVERSIZE_PAIR: some file has
+ * it.  DLSM_OUTPUT_INPUT_FLAGGED: merged.flags is non-zero (the run is not a
+ * whole run) or the device's n_out > pair_cap; then, and with
+ * DLSM_TABLE_SHORT_KEY, DLSM_TABLE_PAIR_TOO_BIG or DLSM_TABLE_INDEX_TOO_BIG
+ * (some file's contents pass 4 GiB), only `built` is written, of it only flags
+ * specified.  A run that cuts into more than DLSM_OUTPUT_MAX_FILES files sets
+ * DLSM_OUTPUT_FILE_CAP; n_files and data_bytes stay exact, the files below the
+ * maximum are written and index_bytes / n_chunks cover those.
+ * pair_cap is the host's bound on n_out (keys.n of the input): it sizes the
+ * grids and the workspace.  pair_cap > UINT32_MAX or file_cap >
+ * DLSM_OUTPUT_MAX_FILES returns DLSM_E_ARG before any launch.
+ * DLSM_OPT_FAULT_INJECT makes the calls return the injected error.
+ * dlsm_compaction_output_dev: every pointer device memory (merged included);
+ * asynchronous on the context's stream: eight launches whatever the run and
+ * the file count are (size, offsets, cut chain, entry lengths beside the
+ * per-file chunk counts, region write beside the chunk ends and the records,
+ * index write, and the seal's two), no host read-back, no counter shared
+ * between workgroups, no result that depends on the order of atomics.  The cut
+ * chain is one hop per file in one wave, each file's chunk chain one hop per
+ * chunk in a wave of its own.
+ * dlsm_compaction_output: every pointer host memory; the cut rule and
+ * dlsm_table_build per file on the host (no device is touched; ctx may be
+ * NULL), synchronous. */
+#define DLSM_OUTPUT_MAX_FILES 4096u /* the cut table of a call sits in LDS (16 KiB of u32) */
+#define DLSM_OUTPUT_DATA_CAP 1u
+#define DLSM_OUTPUT_INDEX_CAP 2u
+#define DLSM_OUTPUT_CHUNK_CAP 4u
+#define DLSM_OUTPUT_FILE_CAP 128u
+#define DLSM_OUTPUT_INPUT_FLAGGED 256u
+typedef struct {
+  dlsm_keyset keys;          /* the run's internal keys; keys.n is pair_cap */
+  const uint8_t* values;
+  const uint64_t* value_off; /* u64[pair_cap + 1], or NULL: every value is value_len bytes */
+  uint32_t value_len;
+  const dlsm_merged* merged; /* the merge's record: n_out pairs are taken, flags must be 0 */
+  uint64_t max_file_bytes;   /* MaxOutputFileSize(); 0: one file */
+  uint64_t chunk_bytes;      /* as dlsm_table_input's */
+} dlsm_output_input;
+typedef struct {
+  uint64_t first, n, data_base, data_bytes, index_base, index_bytes, chunk_base, n_chunks, flags;
+} dlsm_output_file;
+typedef struct {
+  uint64_t n_files, data_bytes, index_bytes, n_chunks, flags;
+} dlsm_output_built;
+typedef struct {
+  uint8_t* data;           /* the files' regions; 16-byte aligned */
+  uint64_t data_cap;
+  uint8_t* index;          /* the files' sealed blocks; 16-byte aligned */
+  uint64_t index_cap;
+  uint64_t* chunk_end;     /* the files' running chunk ends, each file's counted from its start */
+  uint64_t chunk_cap;
+  dlsm_output_file* files; /* [file_cap] */
+  uint64_t file_cap;
+  dlsm_output_built* built;
+} dlsm_output_output;
+
+int dlsm_compaction_output_dev(dlsm_ctx* ctx, const dlsm_output_input* in, const dlsm_output_output* out);
+int dlsm_compaction_output(dlsm_ctx* ctx, const dlsm_output_input* in, const dlsm_output_output* out);
+/* Host only: capacities that no output of a run of at most pair_cap pairs with
+ * key_bytes and value_bytes in all passes (any of the four may be NULL). */
+int dlsm_compaction_output_bound(uint64_t pair_cap, uint64_t key_bytes, uint64_t value_bytes, uint64_t max_file_bytes,
+                                 uint64_t chunk_bytes, uint64_t* data_cap, uint64_t* index_cap, uint64_t* chunk_cap,
+                                 uint64_t* file_cap);
+/* The last dlsm_compaction_output_dev of the context, once its work has
+ * completed: launch_ms[7] (or NULL) gets the device time of the size, offsets,
+ * cut, entries, region and index launches and of the seal, from events
+ * recorded around them; *write_wgs (or NULL) the persistent grid of the two
+ * writes. */
+int dlsm_compaction_output_stats(const dlsm_ctx* ctx, double* launch_ms, uint32_t* write_wgs);
+
 /* ---- legacy FilterPolicy format (util/bloom.cc) ------------------------- */
 
 /* CreateFilter(keys, n, dst) per job: writes bytes+1 bytes at out.
