@@ -38,6 +38,8 @@ __all__ = [
     "compaction_merge", "merge_tile", "merge_span", "merge_chunk", "MERGE_KEEP_ALL", "MERGE_DROP_HIDDEN",
     "compaction_merge_tables", "MERGE_TABLE_MISMATCH",
     "compaction_output", "compaction_output_bound", "output_tables", "OUTPUT_FILE_FIELDS", "OUTPUT_MAX_FILES", "OUTPUT_FILE_CAP", "OUTPUT_INPUT_FLAGGED",
+    "compaction_filters", "compaction_filters_bound", "filter_blocks", "FILTER_REC_FIELDS", "FILTERS_MAX_SLICES", "FILTERS_CAP",
+    "FILTERS_TOO_MANY_LINES", "FILTERS_INPUT_FLAGGED",
 ]
 
 PATH_AUTO, PATH_DIRECT, PATH_SLICED = 0, 1, 2
@@ -370,6 +372,60 @@ def compaction_output(keys: "Keys", values: np.ndarray, merged, *, value_off: Op
     b = tuple(int(x) for x in built)
     files = files[:min(b[0], file_cap)]
     return output_tables(data[:data_cap], index[:index_cap], ends[:chunk_cap], files), files, b
+
+
+FILTERS_MAX_SLICES, FILTERS_CAP, FILTERS_TOO_MANY_LINES, FILTERS_INPUT_FLAGGED = 512, 1, 2, 256
+FILTER_REC_FIELDS = ("base", "bytes", "n_distinct", "num_lines")  # a dlsm_output_filter: four uint64
+
+
+def compaction_filters_bound(pair_cap: int, file_cap: int, bits_per_key: int = 10) -> int:
+    """filters_cap that the filter blocks of no cut of such a run pass."""
+    v = C.c_uint64()
+    check(lib().dlsm_compaction_filters_bound(pair_cap, file_cap, bits_per_key, C.byref(v)), "compaction_filters_bound")
+    return int(v.value)
+
+
+def _filters_io(keys: "Keys", merged, files, out_built, file_cap, bits_per_key: int, filters, filters_cap, recs, built):
+    file_cap = _nbytes(files) // 72 if file_cap is None else int(file_cap)
+    filters_cap = _nbytes(filters) if filters_cap is None else int(filters_cap)
+    for x, nb, what in ((files, 72 * file_cap, "files"), (recs, 32 * file_cap, "recs"), (filters, filters_cap, "filters"),
+                        (merged, 40, "merged"), (out_built, 40, "out_built"), (built, 24, "built")):
+        _need(x, nb, what)
+    fi = _L.dlsm_filters_input(keys.c(), _ptr(merged), _ptr(files), _ptr(out_built), file_cap, bits_per_key)
+    fo = _L.dlsm_filters_output(_ptr(filters), filters_cap, _ptr(recs), _ptr(built))
+    return fi, fo
+
+
+def compaction_filters(keys: "Keys", merged, files, out_built, *, bits_per_key: int = 10,
+                       filters_cap: Optional[int] = None, ctx: Optional["Context"] = None):
+    """The host form of the compaction filters (dlsm_compaction_filters; no
+    device is touched): the run as compaction_output took it, and the file
+    records (uint64[F, 9]) and totals it returned.  Returns (blocks, recs,
+    built): the sealed filter block of every file that lies below
+    ``filters_cap`` (uint8 each, None for one that does not), the records
+    (uint64[F, 4], FILTER_REC_FIELDS) and built = (n_files, filter_bytes,
+    flags).  filters_cap defaults to dlsm_compaction_filters_bound's."""
+    files = np.ascontiguousarray(files, dtype=np.uint64).reshape(-1, 9)
+    file_cap = len(files)
+    if filters_cap is None:
+        filters_cap = compaction_filters_bound(keys.n, file_cap, bits_per_key)
+    filters, recs = np.zeros(max(filters_cap, 1), dtype=np.uint8), np.zeros((max(file_cap, 1), 4), dtype=np.uint64)
+    built = np.zeros(3, dtype=np.uint64)
+    fi, fo = _filters_io(keys, np.ascontiguousarray(merged, dtype=np.uint64), files if file_cap else np.zeros(9, np.uint64),
+                         np.ascontiguousarray(out_built, dtype=np.uint64), file_cap, bits_per_key, filters, filters_cap,
+                         recs, built)
+    check(lib().dlsm_compaction_filters(ctx.h if ctx is not None else None, C.byref(fi), C.byref(fo)),
+          "compaction_filters")
+    b = tuple(int(x) for x in built)
+    recs = recs[:b[0]]
+    return filter_blocks(filters[:filters_cap], recs), recs, b
+
+
+def filter_blocks(filters, recs):
+    """Slice a compaction filters call's buffer by its records: the sealed
+    block per file, None for a file that does not lie wholly in the buffer."""
+    end = _nbytes(filters)
+    return [filters[int(r[0]):int(r[0] + r[1])] if int(r[0] + r[1]) <= end else None for r in recs]
 
 
 def output_tables(data, index, chunk_end, files):
@@ -1299,6 +1355,32 @@ class Context:
         ms, wgs = (C.c_double * 7)(), C.c_uint32()
         check(lib().dlsm_compaction_output_stats(self.h, ms, C.byref(wgs)), "compaction_output_stats")
         return tuple(float(x) for x in ms), int(wgs.value)
+
+    # -- compaction filters: the sealed filter block of every output file ------------
+    def compaction_filters_dev(self, keys: Keys, merged, files, out_built, filters, recs, built, *, bits_per_key: int = 10,
+                               file_cap: Optional[int] = None, filters_cap: Optional[int] = None):
+        """Write the sealed filter block of every file compaction_output_dev
+        cut out of the run: ``keys`` (keys.n the pair capacity) and ``merged``
+        as that call took them, ``files`` and ``out_built`` the records and
+        totals it wrote -- all device memory, read on the device.  filters
+        (device uint8, 16-byte aligned), recs (device uint64[file_cap * 4],
+        FILTER_REC_FIELDS) and built (device uint64[3]: n_files, filter_bytes,
+        flags) are written; the caps default to the buffers' lengths.
+        Asynchronous, no host read-back."""
+        fi, fo = _filters_io(keys, merged, files, out_built, file_cap, bits_per_key, filters, filters_cap, recs, built)
+        check(lib().dlsm_compaction_filters_dev(self.h, C.byref(fi), C.byref(fo)), "compaction_filters_dev")
+
+    def compaction_filters(self, keys: Keys, merged, files, out_built, **kw):
+        """The host-memory form (see dlsm_amd.compaction_filters)."""
+        return compaction_filters(keys, merged, files, out_built, ctx=self, **kw)
+
+    def compaction_filters_stats(self):
+        """(hash, plan, partition, slice, finish) device milliseconds of the
+        last compaction_filters_dev (call after sync), its lgR (2^lgR lines per
+        slice) and the slice launch's grid in workgroups."""
+        ms, lg, wgs = (C.c_double * 5)(), C.c_int(), C.c_uint32()
+        check(lib().dlsm_compaction_filters_stats(self.h, ms, C.byref(lg), C.byref(wgs)), "compaction_filters_stats")
+        return tuple(float(x) for x in ms), int(lg.value), int(wgs.value)
 
     def compaction_merge(self, runs, policy: int = MERGE_DROP_HIDDEN, smallest_snapshot: int = 0, **kw):
         """The host-memory form (see dlsm_amd.compaction_merge)."""

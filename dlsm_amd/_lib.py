@@ -83,6 +83,15 @@ class dlsm_output_output(C.Structure):
                 ("built", C.c_void_p)]
 
 
+class dlsm_filters_input(C.Structure):
+    _fields_ = [("keys", dlsm_keyset), ("merged", C.c_void_p), ("files", C.c_void_p), ("built", C.c_void_p),
+                ("file_cap", C.c_uint64), ("bits_per_key", C.c_int)]
+
+
+class dlsm_filters_output(C.Structure):
+    _fields_ = [("filters", C.c_void_p), ("filters_cap", C.c_uint64), ("recs", C.c_void_p), ("built", C.c_void_p)]
+
+
 class dlsm_merge_run(C.Structure):
     _fields_ = [("keys", dlsm_keyset), ("values", C.c_void_p), ("value_off", C.c_void_p), ("value_len", C.c_uint32)]
 
@@ -239,6 +248,10 @@ SIGNATURES = [
     ("dlsm_compaction_output_bound", C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _U64P, _U64P,
                                                _U64P, _U64P]),
     ("dlsm_compaction_output_stats", C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
+    ("dlsm_compaction_filters_dev", C.c_int, [_VP, C.POINTER(dlsm_filters_input), C.POINTER(dlsm_filters_output)]),
+    ("dlsm_compaction_filters", C.c_int, [_VP, C.POINTER(dlsm_filters_input), C.POINTER(dlsm_filters_output)]),
+    ("dlsm_compaction_filters_bound", C.c_int, [C.c_uint64, C.c_uint64, C.c_int, _U64P]),
+    ("dlsm_compaction_filters_stats", C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
     ("dlsm_compaction_merge_dev", C.c_int, [_VP, C.POINTER(dlsm_merge_run), C.c_int, C.c_int, C.c_uint64,
                                             C.POINTER(dlsm_merge_output)]),
     ("dlsm_compaction_merge", C.c_int, [_VP, C.POINTER(dlsm_merge_run), C.c_int, C.c_int, C.c_uint64,

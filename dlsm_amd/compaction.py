@@ -94,3 +94,16 @@ def open_output(ctx, data, index, chunk_end, files):
         begin = [0] + [int(e) for e in ends[:-1]]
         chunks.append([d[b:int(e)] for b, e in zip(begin, ends)])
     return dlsm_amd.TableIndex(ctx, blocks, on_device=True), dlsm_amd.TableData(ctx, chunks, on_device=True)
+
+
+def open_filters(ctx, filters, recs, verify_checksums=True):
+    """Open what ``Context.compaction_filters_dev`` wrote where it lies:
+    ``filters`` is the call's device tensor, ``recs`` a host copy of its
+    records (one read).  A filter set holds at most 64 filters, so the result
+    is a list of FilterSets: file f is filter f % 64 of set f // 64.  The
+    blocks' checksums are verified on the device."""
+    import dlsm_amd
+
+    blocks = dlsm_amd.filter_blocks(filters, recs)
+    return [dlsm_amd.FilterSet(ctx, blocks[g:g + 64], on_device=True, sealed=True, verify_checksums=verify_checksums)
+            for g in range(0, len(blocks), 64)]

@@ -169,6 +169,11 @@ struct dlsm_ctx {
   DevBuf<uint8_t> co_ws;     // compaction output: offsets, entry starts, per-file tables (plan::CompactionOutputPlan's layout)
   hipEvent_t ev_co[8] = {};  // compaction output: around its launches (dlsm_compaction_output_stats)
   bool co_timed = false;     // the last dlsm_compaction_output_dev recorded all eight
+  DevBuf<uint8_t> cf_ws;     // compaction filters: hashes, entries, per-file tables (plan::CompactionFiltersPlan's layout)
+  hipEvent_t ev_cf[6] = {};  // compaction filters: around its five launches (dlsm_compaction_filters_stats)
+  bool cf_timed = false;     // the last dlsm_compaction_filters_dev recorded all six
+  int cf_lgR = 0;            // ... its slice geometry
+  uint32_t cf_slice_wgs = 0;  // ... and its slice grid
   DevBuf<uint8_t> cm_ws;      // compaction merge: table, records, offsets, partial sums (plan::CompactionMergePlan's layout)
   hipEvent_t ev_cm[2 * kCmMaxPasses + 5] = {};  // compaction merge: around every launch (dlsm_compaction_merge_stats)
   uint32_t cm_passes = 0;     // ... the last call's merge passes
@@ -605,6 +610,7 @@ int dlsm_ctx_destroy(dlsm_ctx* ctx) {
   ctx->tb_ws.release();
   ctx->cm_ws.release();
   ctx->co_ws.release();
+  ctx->cf_ws.release();
   ctx->sel.release();
   ctx->st_keys.release();
   ctx->st_offs.release();
@@ -628,6 +634,8 @@ int dlsm_ctx_destroy(dlsm_ctx* ctx) {
   for (hipEvent_t e : ctx->ev_co)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->ev_cm)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : ctx->ev_cf)
     if (e) (void)hipEventDestroy(e);
   if (ctx->ev_ing0) (void)hipEventDestroy(ctx->ev_ing0);
   if (ctx->ev_ing1) (void)hipEventDestroy(ctx->ev_ing1);
@@ -838,7 +846,7 @@ int dlsm_ctx_stats(dlsm_ctx* ctx, uint64_t* device_allocs, uint64_t* device_byte
   add(ctx->vgl); add(ctx->vabyte); add(ctx->vplan); add(ctx->plan_ws); add(ctx->route_ws);
   add(ctx->st_keys); add(ctx->st_offs); add(ctx->st_out); add(ctx->st_len); add(ctx->st_filter);
   add(ctx->crc_streams); add(ctx->crc_partial); add(ctx->crc_tabs); add(ctx->crc_outp); add(ctx->crc_cap);
-  add(ctx->crc_val); add(ctx->sel); add(ctx->kv_ws); add(ctx->tb_ws); add(ctx->cm_ws); add(ctx->co_ws);
+  add(ctx->crc_val); add(ctx->sel); add(ctx->kv_ws); add(ctx->tb_ws); add(ctx->cm_ws); add(ctx->co_ws); add(ctx->cf_ws);
   if (device_allocs) *device_allocs = n;
   if (device_bytes) *device_bytes = b;
   return DLSM_OK;
@@ -3451,6 +3459,161 @@ int dlsm_compaction_output(dlsm_ctx* ctx, const dlsm_output_input* in, const dls
   B.n_chunks = chunks;
   B.flags |= (B.data_bytes > out->data_cap ? kTbDataCap : 0) | (B.index_bytes > out->index_cap ? kTbIndexCap : 0) |
              (chunks > out->chunk_cap ? kTbChunkCap : 0) | (files > out->file_cap || files > kCoMaxFiles ? kCoFileCap : 0);
+  *out->built = B;
+  return DLSM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Compaction filters: the sealed filter block of every file of a cut run
+// (TableBuilder::Add / FinishFilterBlock, table/table_builder_computeside.cc:
+// 222-224, 389-432; compaction_filters.hip)
+// ---------------------------------------------------------------------------
+int dlsm_compaction_filters_bound(uint64_t pair_cap, uint64_t file_cap, int bits_per_key, uint64_t* filters_cap) {
+  return plan_compaction_filters_bound(pair_cap, file_cap, bits_per_key, filters_cap);
+}
+
+static int compaction_filters_args(const dlsm_filters_input* in, const dlsm_filters_output* out) {
+  if (!in || !out || !out->built || !in->merged || !in->built || in->keys.n > 0xffffffffull ||
+      in->file_cap > kCoMaxFiles || in->bits_per_key < 1 || in->bits_per_key > kCfMaxBpk)
+    return DLSM_E_ARG;
+  DLSM_CHECK(validate_keyset(in->keys));
+  if (in->keys.n && !in->keys.offsets && in->keys.key_len < 8) return DLSM_E_ARG;
+  if ((out->filters_cap && !out->filters) || (in->file_cap && (!in->files || !out->recs))) return DLSM_E_ARG;
+  return DLSM_OK;
+}
+
+int dlsm_compaction_filters_dev(dlsm_ctx* ctx, const dlsm_filters_input* in, const dlsm_filters_output* out) {
+  if (!ctx) return DLSM_E_ARG;
+  DLSM_CHECK(compaction_filters_args(in, out));
+  if (!aligned(out->filters, 16) || !aligned(out->recs, 8) || !aligned(out->built, 8) || !aligned(in->files, 8) ||
+      !aligned(in->built, 8) || !aligned(in->merged, 8) || !aligned(in->keys.offsets, 8))
+    return DLSM_E_ARG;
+  CompactionFiltersPlan P;
+  DLSM_CHECK(plan_compaction_filters(in->keys.n, in->file_cap, in->bits_per_key, P));
+  if (ctx->fault) return -ctx->fault;
+  DeviceGuard g(ctx->device);
+  for (hipEvent_t& e : ctx->ev_cf)
+    if (!e) DLSM_TRY(hipEventCreate(&e));
+  ctx->cf_timed = false;
+  DLSM_CHECK(ctx->cf_ws.ensure(P.bytes));
+  uint8_t* ws = ctx->cf_ws.p;
+  CfDev a{};
+  a.kbytes = in->keys.bytes;
+  a.koff = in->keys.offsets;
+  a.klen = in->keys.key_len;
+  a.bpk = in->bits_per_key;
+  a.k = full_num_probes(in->bits_per_key);
+  a.lgR = P.lgR;
+  a.merged = reinterpret_cast<const uint64_t*>(in->merged);
+  a.files = reinterpret_cast<const CoFile*>(in->files);
+  a.built_in = reinterpret_cast<const uint64_t*>(in->built);
+  a.pair_cap = in->keys.n;
+  a.file_cap = in->file_cap;
+  a.filters = out->filters;
+  a.filters_cap = out->filters_cap;
+  a.recs = reinterpret_cast<CfRec*>(out->recs);
+  a.built = reinterpret_cast<uint64_t*>(out->built);
+  a.tot = reinterpret_cast<uint64_t*>(ws + P.tot_off);
+  a.hash = reinterpret_cast<uint32_t*>(ws + P.hash_off);
+  a.ccnt = reinterpret_cast<uint32_t*>(ws + P.ccnt_off);
+  a.cscan = reinterpret_cast<uint32_t*>(ws + P.cscan_off);
+  a.gpre = reinterpret_cast<uint32_t*>(ws + P.gpre_off);
+  a.cut = reinterpret_cast<uint32_t*>(ws + P.cut_off);
+  a.fL = reinterpret_cast<uint32_t*>(ws + P.fL_off);
+  a.fmagic = reinterpret_cast<uint32_t*>(ws + P.fmagic_off);
+  a.fsl0 = reinterpret_cast<uint32_t*>(ws + P.fsl0_off);
+  a.fbase = reinterpret_cast<uint64_t*>(ws + P.fbase_off);
+  a.clo = reinterpret_cast<uint32_t*>(ws + P.clo_off);
+  a.tab = reinterpret_cast<uint16_t*>(ws + P.tab_off);
+  a.region = reinterpret_cast<uint32_t*>(ws + P.region_off);
+  a.partial = reinterpret_cast<uint32_t*>(ws + P.partial_off);
+  a.chunks = P.chunks;
+  a.slice_wgs = P.slice_wgs;
+  DLSM_TRY(launch_compaction_filters(a, ctx->ev_cf, ctx->stream));
+  ctx->cf_timed = true;
+  ctx->cf_lgR = P.lgR;
+  ctx->cf_slice_wgs = P.slice_wgs;
+  return DLSM_OK;
+}
+static_assert(sizeof(dlsm_output_filter) == sizeof(CfRec), "the filter record is the kernels' CfRec");
+static_assert(DLSM_FILTERS_MAX_SLICES == kCfMaxSlices && DLSM_FILTERS_CAP == kCfCap &&
+                  DLSM_FILTERS_TOO_MANY_LINES == kCfTooManyLines && DLSM_FILTERS_INPUT_FLAGGED == kCfInputFlagged,
+              "the header's constants are the kernels'");
+
+int dlsm_compaction_filters_stats(const dlsm_ctx* ctx, double* launch_ms, int* lgR, uint32_t* slice_wgs) {
+  if (!ctx) return DLSM_E_ARG;
+  if (lgR) *lgR = ctx->cf_lgR;
+  if (slice_wgs) *slice_wgs = ctx->cf_slice_wgs;
+  if (launch_ms) {
+    for (int j = 0; j < 5; j++) launch_ms[j] = 0;
+    if (!ctx->cf_timed) return DLSM_OK;
+    DeviceGuard g(ctx->device);
+    for (int j = 0; j < 5; j++) {
+      float ms = 0;
+      DLSM_TRY(hipEventElapsedTime(&ms, ctx->ev_cf[j], ctx->ev_cf[j + 1]));
+      launch_ms[j] = ms;
+    }
+  }
+  return DLSM_OK;
+}
+
+// The host form: BloomHash of every pair's user key, then file by file the
+// consecutive-distinct count, the line count, AddHash into the block where it
+// fits, the two trailers.
+int dlsm_compaction_filters(dlsm_ctx* ctx, const dlsm_filters_input* in, const dlsm_filters_output* out) {
+  DLSM_CHECK(compaction_filters_args(in, out));
+  if (ctx && ctx->fault) return -ctx->fault;
+  const uint64_t n = in->merged->n_out, F = in->built->n_files;
+  bool bad = in->merged->flags != 0 || n > in->keys.n || (in->built->flags & ~kCfBuiltOk) != 0 || F > in->file_cap ||
+             (F == 0 && n != 0);
+  for (uint64_t f = 0; f < F && !bad; f++) {
+    const uint64_t first = in->files[f].first, cnt = in->files[f].n;
+    bad = first >= n || cnt == 0 || cnt > n || first + cnt != (f + 1 < F ? in->files[f + 1].first : n) || (f == 0 && first != 0);
+  }
+  dlsm_filters_built B{};
+  if (bad) {
+    B.flags = kCfInputFlagged;
+    *out->built = B;
+    return DLSM_OK;
+  }
+  const int bpk = in->bits_per_key, k = full_num_probes(bpk);
+  const int lgR = filters_lgR(in->keys.n, in->file_cap, bpk);
+  const dlsm_keyset& K = in->keys;
+  std::vector<uint32_t> h;
+  for (uint64_t f = 0; f < F; f++) {
+    const uint64_t first = in->files[f].first, cnt = in->files[f].n;
+    h.resize(cnt);
+    uint64_t D = 0;
+    for (uint64_t j = 0; j < cnt; j++) {
+      const uint64_t i = first + j;
+      const uint64_t at = K.offsets ? K.offsets[i] : i * K.key_len, len = K.offsets ? K.offsets[i + 1] - at : K.key_len;
+      h[j] = bloom_hash_host(K.bytes + at, len >= 8 ? len - 8 : 0);
+      D += j == 0 || h[j] != h[j - 1];
+    }
+    const uint32_t L = full_num_lines(D, bpk, nullptr);
+    const uint64_t bytes = cf_block_bytes(L), base = B.filter_bytes;
+    const bool over = cf_slices(L, lgR) > kCfMaxSlices;
+    out->recs[f] = dlsm_output_filter{base, bytes, D, L};
+    B.filter_bytes += co_pad16(bytes);
+    if (over) B.flags |= kCfTooManyLines;
+    if (over || base + bytes > out->filters_cap) continue;
+    uint8_t* blk = out->filters + base;
+    memset(blk, 0, 64ull * L);
+    for (uint64_t j = 0; j < cnt; j++) {
+      uint32_t x = h[j];
+      uint8_t* line = blk + 64ull * (x % L);
+      const uint32_t delta = bloom_delta(x);
+      for (int p = 0; p < k; p++, x += delta) line[(x & 511u) >> 3] |= static_cast<uint8_t>(1u << (x & 7u));
+    }
+    uint8_t* t = blk + 64ull * L;
+    t[0] = static_cast<uint8_t>(static_cast<int8_t>(k));
+    memcpy(t + 1, &L, 4);
+    t[5] = 0;  // kNoCompression
+    const uint32_t m = dlsm_crc32c_mask(dlsm_crc32c_extend(0, blk, 64ull * L + 6));
+    memcpy(t + 6, &m, 4);
+  }
+  B.n_files = F;
+  if (B.filter_bytes > out->filters_cap) B.flags |= kCfCap;
   *out->built = B;
   return DLSM_OK;
 }

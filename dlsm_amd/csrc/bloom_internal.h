@@ -13,6 +13,7 @@
 #include "shard_route.h"
 #include "table_build.h"
 #include "compaction_output.h"
+#include "compaction_filters.h"
 #include "table_scan.h"
 
 namespace dlsm {
@@ -592,8 +593,43 @@ struct CoDev {
 // ev: eight events recorded around the launches (the seal's two as one), or nullptr.
 hipError_t launch_compaction_output(const CoDev& a, uint32_t index_wgs, uint32_t seal_wgs, hipEvent_t* ev, hipStream_t s);
 
+// compaction_filters.hip: the sealed filter block of every file of a cut run
+// (dlsm_compaction_filters_dev).  Workspace in plan::CompactionFiltersPlan's
+// layout; the per-file tables hold kCoMaxFiles + 1 values each.
+struct CfDev {
+  const uint8_t* kbytes;     // the run's internal keys
+  const uint64_t* koff;      // u64[pair_cap + 1], or nullptr: every key is klen bytes
+  uint32_t klen;
+  int32_t bpk, k, lgR;       // bits per key, the probe count, 2^lgR lines per slice
+  const uint64_t* merged;    // dlsm_merged on the device: n_out at [1], flags at [4]
+  const CoFile* files;       // dlsm_output_file[file_cap]: first and n are read
+  const uint64_t* built_in;  // dlsm_output_built on the device: n_files at [0], flags at [4]
+  uint64_t pair_cap, file_cap;
+  uint8_t* filters;          // 16-byte aligned
+  uint64_t filters_cap;
+  CfRec* recs;               // dlsm_output_filter[file_cap]
+  uint64_t* built;           // dlsm_filters_built: n_files, filter_bytes, flags
+  uint64_t* tot;             // workspace u64[8]: what the plan launch hands on (compaction_filters.hip)
+  uint32_t* hash;            // workspace u32[pair_cap]: BloomHash of every pair's user key
+  uint32_t* ccnt;            // workspace u32[chunks]: a chunk's pairs that count (a file's first, or a new hash)
+  uint32_t* cscan;           // workspace u32[chunks + 1]: their exclusive sum
+  uint32_t* gpre;            // workspace, per file: the counting pairs of its first pair's chunk in front of that pair
+  uint32_t* cut;             // ... the first pair; [nf]: n
+  uint32_t* fL;              // ... the line count
+  uint32_t* fmagic;          // ... fastmod_magic of it
+  uint32_t* fsl0;            // ... the flat slices in front of the file; [nf]: their total
+  uint64_t* fbase;           // ... the block's place
+  uint32_t* clo;             // workspace u32[chunks]: the flat slice id of a chunk's bin 0
+  uint16_t* tab;             // workspace u16[chunks * (kCfMaxBins + 1)]: a chunk's bins' first units
+  uint32_t* region;          // workspace u32[chunks * kCfRegion]: a chunk's entries, bin by bin
+  uint32_t* partial;         // workspace u32[slice_wgs]: the slices' raw crcs
+  uint32_t chunks, slice_wgs;  // the grids: ceil(pair_cap / kCfChunk) (at least 1), the bound on flat slices
+};
+// ev: six events recorded around the five launches, or nullptr.
+hipError_t launch_compaction_filters(const CfDev& a, hipEvent_t* ev, hipStream_t s);
+
 // compaction_merge.hip: R sorted runs into one run in the table build's input
-// form (dlsm_compaction_merge_dev).  Workspace in plan::CompactionMergePlan's
+// form (dlsm_compaction_merge_dev). Workspace in plan::CompactionMergePlan's
 // layout; the record buffer the last pass did not write holds the decide
 // pass's lengths and the gather's source addresses (4 x u64[n]).
 struct CmDev {

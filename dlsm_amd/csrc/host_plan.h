@@ -1145,6 +1145,78 @@ inline int plan_compaction_output_bound(uint64_t pair_cap, uint64_t key_bytes, u
   return DLSM_OK;
 }
 
+// ---- compaction filters (compaction_filters.hip) -------------------------------
+// A file of n pairs has at most n * bpk / 512 + 2 lines (the u32 product of
+// full_num_lines only wraps downwards): ceil, then made odd.
+inline uint64_t filters_max_lines(uint64_t n, int bpk) { return n * static_cast<uint64_t>(bpk) / kLineBits + 2; }
+
+// The lines per slice of a call, 2^lgR: the smallest slice (the most
+// workgroups for a short file) at which no file of pair_cap pairs passes
+// kCfMaxSlices slices, else the largest; a file that still passes is flagged.
+// file_cap does not move the choice: a file may hold the whole run.
+inline int filters_lgR(uint64_t pair_cap, uint64_t file_cap, int bpk) {
+  (void)file_cap;
+  for (int lg = kCfMinLgR; lg < kCfMaxLgR; lg++)
+    if (filters_max_lines(pair_cap, bpk) <= (static_cast<uint64_t>(kCfMaxSlices) << lg)) return lg;
+  return kCfMaxLgR;
+}
+
+// The most flat slices of a call: a built file has at most
+// 1 + (n * bpk / 512 + 1) / R of them, summed over at most F files of
+// pair_cap pairs together.
+inline uint64_t filters_slice_bound(uint64_t pair_cap, uint64_t file_cap, int bpk, int lgR) {
+  const uint64_t F = std::min(pair_cap, file_cap);
+  return F + ((pair_cap * static_cast<uint64_t>(bpk) / kLineBits + F) >> lgR) + 1;
+}
+
+// dlsm_compaction_filters_bound: a block is 64 L + 10 bytes with
+// 64 L <= n * bpk / 8 + 128, and up to 15 pad bytes follow it.
+inline int plan_compaction_filters_bound(uint64_t pair_cap, uint64_t file_cap, int bpk, uint64_t* filters_cap) {
+  if (pair_cap > 0xffffffffull || file_cap > kCoMaxFiles || bpk < 1 || bpk > kCfMaxBpk) return DLSM_E_ARG;
+  if (filters_cap) *filters_cap = pair_cap * static_cast<uint64_t>(bpk) / 8 + (128 + 10 + 15) * std::min(pair_cap, file_cap);
+  return DLSM_OK;
+}
+
+// dlsm_compaction_filters_dev from the host's bounds alone: the slice
+// geometry, the two grids (a workgroup per chunk of kCfChunk pairs, at least
+// one; a workgroup per flat slice) and the workspace layout (byte offsets,
+// every region 256-byte aligned): 4 bytes of hash per pair, 64 KiB of entries
+// and a bin table per chunk, and the per-file tables.
+struct CompactionFiltersPlan {
+  int lgR = 0;
+  uint32_t chunks = 0, slice_wgs = 0;
+  uint64_t tot_off = 0, hash_off = 0, ccnt_off = 0, cscan_off = 0, gpre_off = 0, cut_off = 0, fL_off = 0, fmagic_off = 0,
+           fsl0_off = 0, fbase_off = 0, clo_off = 0, tab_off = 0, region_off = 0, partial_off = 0;
+  uint64_t bytes = 0;
+};
+
+inline int plan_compaction_filters(uint64_t pair_cap, uint64_t file_cap, int bpk, CompactionFiltersPlan& P) {
+  if (pair_cap > 0xffffffffull || file_cap > kCoMaxFiles || bpk < 1 || bpk > kCfMaxBpk) return DLSM_E_ARG;
+  P = CompactionFiltersPlan();
+  P.lgR = filters_lgR(pair_cap, file_cap, bpk);
+  P.chunks = std::max<uint32_t>(ceil_div_u32(pair_cap, kCfChunk), 1);
+  P.slice_wgs = static_cast<uint32_t>(filters_slice_bound(pair_cap, file_cap, bpk, P.lgR));
+  const uint64_t F = kCoMaxFiles + 1, C = P.chunks;
+  uint64_t unused;
+  Layout ws;
+  ws.region(&P.tot_off, &unused, sizeof(uint64_t) * 8);
+  ws.region(&P.hash_off, &unused, sizeof(uint32_t) * pair_cap);
+  ws.region(&P.ccnt_off, &unused, sizeof(uint32_t) * C);
+  ws.region(&P.cscan_off, &unused, sizeof(uint32_t) * (C + 1));
+  ws.region(&P.gpre_off, &unused, sizeof(uint32_t) * F);
+  ws.region(&P.cut_off, &unused, sizeof(uint32_t) * F);
+  ws.region(&P.fL_off, &unused, sizeof(uint32_t) * F);
+  ws.region(&P.fmagic_off, &unused, sizeof(uint32_t) * F);
+  ws.region(&P.fsl0_off, &unused, sizeof(uint32_t) * F);
+  ws.region(&P.fbase_off, &unused, sizeof(uint64_t) * F);
+  ws.region(&P.clo_off, &unused, sizeof(uint32_t) * C);
+  ws.region(&P.tab_off, &unused, sizeof(uint16_t) * C * (kCfMaxBins + 1));
+  ws.region(&P.region_off, &unused, sizeof(uint32_t) * C * kCfRegion);
+  ws.region(&P.partial_off, &unused, sizeof(uint32_t) * P.slice_wgs);
+  P.bytes = ws.at;
+  return DLSM_OK;
+}
+
 // ---- compaction merge (compaction_merge.hip) -----------------------------------
 // dlsm_compaction_merge_dev from the runs' pair counts alone: the runs' bases,
 // ceil(log2 R) passes of two-way merges -- pass p pairs neighbouring segments

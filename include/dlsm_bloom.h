@@ -1166,6 +1166,92 @@ int dlsm_compaction_output_bound(uint64_t pair_cap, uint64_t key_bytes, uint64_t
  * writes. */
 int dlsm_compaction_output_stats(const dlsm_ctx* ctx, double* launch_ms, uint32_t* write_wgs);
 
+/* The filter blocks of a compaction's output files.  Every output file's
+ * TableBuilder feeds ExtractUserKey(key) of each Add to a
+ * FullFilterBlockBuilder and writes [filter][type 0][masked crc32c] at Finish
+ * (table/table_builder_computeside.cc:222-224, :389-432).  The call takes the
+ * run as dlsm_compaction_output* took it and the file records and dlsm_output_built
+ * it wrote -- both, like merged, read ON THE DEVICE -- and writes every file's
+ * sealed filter block.  Each output is a pure function of the inputs:
+ *   per file: for f < n_files the block at filters + recs[f].base is byte for
+ *   byte what dlsm_bloom_full_build_block gives for keys [files[f].first,
+ *   + files[f].n) of the run alone with suffix_len = 8 (whatever keys.suffix_len
+ *   says) and the exact line count: the AddKey dedup restarts at the file's
+ *   first pair -- a user key whose versions straddle a cut counts once in each
+ *   file -- and num_lines is CalculateSpace of the file's own
+ *   consecutive-distinct count (u32 n * bits_per_key, ceil(/ 512), made odd);
+ *   k is dlsm_bloom_full_num_probes(bits_per_key); the block is the lines, the
+ *   filter's trailer [k][Fixed32 num_lines], then [type 0][masked crc32c]:
+ *   bytes = 64 num_lines + 10;
+ *   placement: base is the exclusive sum of bytes rounded up to 16, so every
+ *   block opens where it lies with dlsm_filterset_create_blocks /
+ *   dlsm_version_create_blocks (blocks_are_device = 1).  The pad bytes are not
+ *   written;
+ *   recs[f] = base, bytes, n_distinct, num_lines for every f < n_files;
+ *   built: n_files; filter_bytes, the sum of the padded lengths; flags.  All
+ *   exact whatever filters_cap is.
+ * flags: DLSM_FILTERS_CAP where filter_bytes > filters_cap: a block that does
+ * not lie wholly below filters_cap is not written at all, every other block
+ * is the right bytes, and nothing is ever written at or past filters_cap.
+ * DLSM_FILTERS_TOO_MANY_LINES: some file has more than
+ * DLSM_FILTERS_MAX_SLICES << lgR lines, lgR (7..9) the slice geometry the call
+ * chose from pair_cap and bits_per_key (dlsm_compaction_filters_stats): at
+ * lgR = 9, 262,144 lines, a 16 MiB filter.  Such a file's record is exact and
+ * its block is not written; a call is sized so that no file of pair_cap pairs
+ * reaches the limit unless pair_cap * bits_per_key passes 2^27.
+ * DLSM_FILTERS_INPUT_FLAGGED: merged.flags is non-zero, n_out > keys.n,
+ * built.flags carries anything but DLSM_OUTPUT_DATA_CAP / INDEX_CAP /
+ * CHUNK_CAP, n_files > file_cap (the records stop before n_files), or the
+ * records are not n_files non-empty files that cover [0, n_out) back to back;
+ * then only `built` is written, its counts 0.
+ * keys.n (pair_cap) > UINT32_MAX, file_cap > DLSM_OUTPUT_MAX_FILES,
+ * bits_per_key outside 1..512 or a filters pointer that is not 16-byte
+ * aligned returns DLSM_E_ARG before any launch.  DLSM_OPT_FAULT_INJECT makes
+ * the calls return the injected error.
+ * dlsm_compaction_filters_dev: every pointer device memory; asynchronous on
+ * the context's stream: five launches whatever the run and the file count are
+ * (hash, plan, partition, slice, finish), their grids sized by pair_cap and
+ * file_cap alone, no host read-back, no counter shared between workgroups, no
+ * result that depends on the order of atomics.
+ * dlsm_compaction_filters: every pointer host memory; the same rules on the
+ * host (no device is touched; ctx may be NULL), synchronous. */
+#define DLSM_FILTERS_MAX_SLICES 512u
+#define DLSM_FILTERS_CAP 1u
+#define DLSM_FILTERS_TOO_MANY_LINES 2u
+#define DLSM_FILTERS_INPUT_FLAGGED 256u
+typedef struct {
+  dlsm_keyset keys;               /* the run's internal keys, as dlsm_output_input.keys; keys.n is pair_cap */
+  const dlsm_merged* merged;      /* n_out and flags are read */
+  const dlsm_output_file* files;  /* [file_cap] as dlsm_compaction_output* wrote them: first and n are read */
+  const dlsm_output_built* built; /* n_files and flags are read */
+  uint64_t file_cap;
+  int bits_per_key;
+} dlsm_filters_input;
+typedef struct {
+  uint64_t base, bytes, n_distinct, num_lines;
+} dlsm_output_filter;
+typedef struct {
+  uint64_t n_files, filter_bytes, flags;
+} dlsm_filters_built;
+typedef struct {
+  uint8_t* filters;         /* the files' sealed filter blocks; 16-byte aligned */
+  uint64_t filters_cap;
+  dlsm_output_filter* recs; /* [file_cap] */
+  dlsm_filters_built* built;
+} dlsm_filters_output;
+
+int dlsm_compaction_filters_dev(dlsm_ctx* ctx, const dlsm_filters_input* in, const dlsm_filters_output* out);
+int dlsm_compaction_filters(dlsm_ctx* ctx, const dlsm_filters_input* in, const dlsm_filters_output* out);
+/* Host only: a capacity that the blocks of no cut of a run of at most pair_cap
+ * pairs into at most file_cap files pass. */
+int dlsm_compaction_filters_bound(uint64_t pair_cap, uint64_t file_cap, int bits_per_key, uint64_t* filters_cap);
+/* The last dlsm_compaction_filters_dev of the context, once its work has
+ * completed: launch_ms[5] (or NULL) gets the device time of the hash, plan,
+ * partition, slice and finish launches from events recorded around them; *lgR
+ * (or NULL) the slice geometry and *slice_wgs (or NULL) the slice launch's
+ * grid. */
+int dlsm_compaction_filters_stats(const dlsm_ctx* ctx, double* launch_ms, int* lgR, uint32_t* slice_wgs);
+
 /* ---- legacy FilterPolicy format (util/bloom.cc) ------------------------- */
 
 /* CreateFilter(keys, n, dst) per job: writes bytes+1 bytes at out.
