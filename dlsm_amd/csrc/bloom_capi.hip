@@ -17,6 +17,7 @@
 
 #include "../../include/dlsm_bloom.h"
 #include "bloom_internal.h"
+#include "crc32c_dev.h"
 #include "host_plan.h"
 
 using namespace dlsm;
@@ -1315,11 +1316,7 @@ namespace {
 struct Crc32cTable {
   uint32_t t[256];
   Crc32cTable() {
-    for (uint32_t i = 0; i < 256; i++) {
-      uint32_t c = i;
-      for (int k = 0; k < 8; k++) c = (c & 1u) ? (c >> 1) ^ 0x82f63b78u : (c >> 1);
-      t[i] = c;
-    }
+    for (uint32_t i = 0; i < 256; i++) t[i] = crc32c::raw_byte(i, 0);
   }
 };
 }  // namespace
@@ -1334,7 +1331,7 @@ uint32_t dlsm_crc32c_extend(uint32_t init_crc, const void* data, size_t n) {
   return ~c;
 }
 
-uint32_t dlsm_crc32c_mask(uint32_t crc) { return ((crc >> 15) | (crc << 17)) + 0xa282ead8u; }
+uint32_t dlsm_crc32c_mask(uint32_t crc) { return crc32c::mask(crc); }
 
 namespace {
 int run_crc(dlsm_ctx* ctx, const std::vector<std::vector<uint8_t>>& streams, int n, uint64_t max_total,

@@ -36,13 +36,17 @@
 // search of the prefix sums, the slice zeroed in LDS, the file's own chunk
 // range walked a wave per chunk, bits set with ds_or (a straight-line unit for
 // k = 6), the slice streamed out with 16-byte stores, and its raw crc32c taken
-// from LDS.
+// from LDS (crc32c_dev.h).
 //
 // Finish (cf_finish_kernel): a thread per file folds its slices' crcs, appends
 // the filter's trailer and the type byte and writes both trailers.
+//
+// The workgroup scans are wg_scan.h's.
 #include <hip/hip_runtime.h>
 
 #include "bloom_internal.h"
+#include "crc32c_dev.h"
+#include "wg_scan.h"
 
 namespace dlsm {
 namespace {
@@ -62,30 +66,6 @@ static_assert(kCfMinLgR >= 6 && (64u << kCfMaxLgR) <= 32768, "the slice's crc sp
 enum { kTotN, kTotNf, kTotSlices };  // tot[]: what the plan hands on
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// The exclusive scan of v over the workgroup; *all: the sum.  sh: a slot per wave.
-template <class T>
-__device__ __forceinline__ T block_scan(T v, T* sh, T* all) {
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  T inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const T up = __shfl_up(inc, d, 64);
-    inc += lane >= static_cast<uint32_t>(d) ? up : 0;
-  }
-  __syncthreads();  // sh may still be read from the call before
-  if (lane == 63) sh[wave] = inc;
-  __syncthreads();
-  T before = 0, sum = 0;
-#pragma unroll
-  for (int w = 0; w < kCfWaves; w++) {
-    const T x = sh[w];
-    before += static_cast<uint32_t>(w) < wave ? x : 0;
-    sum += x;
-  }
-  *all = sum;
-  return before + inc - v;
-}
 
 // The inputs as the device gives them: the cut table into scut (nf + 1 values,
 // scut[nf] = n).  False where the run is flagged, does not fit the grids, or
@@ -217,7 +197,7 @@ __global__ __launch_bounds__(kCfBlock) void cf_hash_kernel(CfDev a) {
     const uint32_t counts = in && (start || h != prev);
     if (in) a.hash[i] = h;
     uint32_t all;
-    const uint32_t pre = block_scan<uint32_t>(counts, sh, &all);
+    const uint32_t pre = block_scan<uint32_t, kCfWaves>(counts, sh, &all);
     if (start) a.gpre[f] = run + pre;
     run += all;
     if (t == 0) hh[0] = last;  // (every prev was read in front of the scan's barriers)
@@ -245,7 +225,7 @@ __global__ __launch_bounds__(kCfBlock) void cf_plan_kernel(CfDev a) {
   for (uint32_t c0 = 0; c0 < nch; c0 += kCfBlock) {
     const uint32_t c = c0 + t;
     uint64_t all;
-    const uint64_t x = total + block_scan<uint64_t>(c < nch ? a.ccnt[c] : 0, sh, &all);
+    const uint64_t x = total + block_scan<uint64_t, kCfWaves>(c < nch ? a.ccnt[c] : 0, sh, &all);
     if (c < nch) a.cscan[c] = static_cast<uint32_t>(x);
     total += all;
   }
@@ -267,9 +247,9 @@ __global__ __launch_bounds__(kCfBlock) void cf_plan_kernel(CfDev a) {
     const uint32_t ns = cf_slices(L, a.lgR);
     const bool over = in && ns > kCfMaxSlices;
     uint64_t ball, sall;
-    const uint64_t base = brun + block_scan<uint64_t>(in ? co_pad16(bytes) : 0, sh, &ball);
+    const uint64_t base = brun + block_scan<uint64_t, kCfWaves>(in ? co_pad16(bytes) : 0, sh, &ball);
     const bool fits = in && !over && base + bytes <= a.filters_cap;
-    const uint64_t sl = srun + block_scan<uint64_t>(fits ? ns : 0, sh, &sall);
+    const uint64_t sl = srun + block_scan<uint64_t, kCfWaves>(fits ? ns : 0, sh, &sall);
     if (in) {
       a.cut[f] = scut[f];
       a.fL[f] = L;
@@ -340,7 +320,7 @@ __global__ __launch_bounds__(kCfBlock) void cf_partition_kernel(CfDev a) {
     units += (cnt[q] + 3) >> 2;
   }
   uint32_t all;
-  uint32_t u = block_scan<uint32_t>(units, sh, &all);  // (its barriers stand between the counts' reads and the writes below)
+  uint32_t u = block_scan<uint32_t, kCfWaves>(units, sh, &all);  // (its barriers stand between the counts' reads and the writes below)
 #pragma unroll
   for (int q = 0; q < kCfBinsPer; q++) {
     if (j0 + q >= nb) break;
@@ -357,43 +337,6 @@ __global__ __launch_bounds__(kCfBlock) void cf_partition_kernel(CfDev a) {
 #pragma unroll
   for (int s = 0; s < kCfSub; s++)
     if (bin[s] != ~0u) reg[4 * hist[bin[s]] + rank[s]] = ent[s];
-}
-
-// ---- crc32c (Castagnoli), the algebra of block_crc.hip --------------------------
-constexpr uint32_t kPoly = 0x82f63b78u;  // reflected
-
-// a(x) * b(x) mod P in the reflected representation (bit 31 = x^0).
-__device__ __forceinline__ uint32_t mulmod(uint32_t x, uint32_t y) {
-  uint32_t p = 0;
-#pragma unroll
-  for (int i = 0; i < 32; i++) {
-    if (x & (0x80000000u >> i)) p ^= y;
-    y = (y & 1u) ? (y >> 1) ^ kPoly : (y >> 1);
-  }
-  return p;
-}
-
-struct XPow {
-  uint32_t p[40];  // x^(2^k) mod P
-};
-
-__device__ __forceinline__ uint32_t xpow(const XPow& xp, uint64_t bits) {
-  uint32_t xn = 0x80000000u;  // x^0
-  for (int k = 0; bits; k++, bits >>= 1)
-    if (bits & 1u) xn = mulmod(xn, xp.p[k]);
-  return xn;
-}
-
-__device__ __forceinline__ uint32_t raw_byte(uint32_t r, uint32_t x) {
-  r ^= x;
-#pragma unroll
-  for (int k = 0; k < 8; k++) r = (r & 1u) ? (r >> 1) ^ kPoly : (r >> 1);
-  return r;
-}
-
-__device__ __forceinline__ uint32_t raw_word(uint32_t r, uint32_t w, const uint32_t* T) {
-  r ^= w;
-  return T[768 + (r & 0xffu)] ^ T[512 + ((r >> 8) & 0xffu)] ^ T[256 + ((r >> 16) & 0xffu)] ^ T[r >> 24];
 }
 
 // AddHash of one entry into the slice: K probes straight-line, or k in a loop (K = 0).
@@ -418,7 +361,7 @@ __device__ __forceinline__ void cf_add(uint32_t* sl, uint32_t e, int k) {
 }
 
 template <int K>
-__global__ __launch_bounds__(kCfSliceBlock) void cf_slice_kernel(CfDev a, XPow xp) {
+__global__ __launch_bounds__(kCfSliceBlock) void cf_slice_kernel(CfDev a, crc32c::XPow xp) {
   __shared__ __attribute__((aligned(16))) uint32_t sl[(64u << kCfMaxLgR) / 4];
   __shared__ uint32_t T[1024];
   __shared__ uint32_t wv[kCfSliceWaves];
@@ -430,17 +373,7 @@ __global__ __launch_bounds__(kCfSliceBlock) void cf_slice_kernel(CfDev a, XPow x
   const uint32_t lines = L - js * R < R ? L - js * R : R;
   uint4* sl4 = reinterpret_cast<uint4*>(sl);
   for (uint32_t q = t; q < lines * 4; q += kCfSliceBlock) sl4[q] = make_uint4(0, 0, 0, 0);
-  {  // the slice-by-4 tables
-    uint32_t c = t;
-    for (int k = 0; k < 8; k++) c = (c & 1u) ? (c >> 1) ^ kPoly : (c >> 1);
-    T[t] = c;
-    __syncthreads();
-    for (int j = 1; j < 4; j++) {
-      const uint32_t prev = T[256 * (j - 1) + t];
-      T[256 * j + t] = (prev >> 8) ^ T[prev & 0xffu];
-      __syncthreads();
-    }
-  }
+  crc32c::build_tables<kCfSliceBlock>(T);
   const uint32_t b = a.cut[f], e = a.cut[f + 1];
   const uint32_t lane = t & 63, wave = t >> 6;
   for (uint32_t c = b / kCfChunk + wave; c <= (e - 1) / kCfChunk; c += kCfSliceWaves) {
@@ -472,18 +405,17 @@ __global__ __launch_bounds__(kCfSliceBlock) void cf_slice_kernel(CfDev a, XPow x
     const int q = static_cast<int>(t) * per + i - lead;
     if (q < 0) continue;
     const uint4 v = sl4[q];
-    acc = raw_word(raw_word(raw_word(raw_word(acc, v.x, T), v.y, T), v.z, T), v.w, T);
+    acc = crc32c::raw_word(acc, v.x, T);
+    acc = crc32c::raw_word(acc, v.y, T);
+    acc = crc32c::raw_word(acc, v.z, T);
+    acc = crc32c::raw_word(acc, v.w, T);
   }
-#pragma unroll
-  for (int k = 0; k < 6; k++) {  // level k joins neighbours of 16 * per * 2^k bytes
-    const uint32_t other = __shfl_xor(acc, 1 << k, 64);
-    if ((lane & (1u << k)) == 0) acc = mulmod(acc, xp.p[a.lgR + 1 + k]) ^ other;
-  }
+  acc = crc32c::wave_fold(acc, xp, a.lgR + 1);  // level k joins neighbours of 16 * per * 2^k bytes
   if (lane == 0) wv[wave] = acc;
   __syncthreads();
   if (t == 0) {
     uint32_t r = 0;
-    for (int w = 0; w < kCfSliceWaves; w++) r = mulmod(r, xp.p[a.lgR + 7]) ^ wv[w];  // a wave is 2^(lgR + 7) bits
+    for (int w = 0; w < kCfSliceWaves; w++) r = crc32c::mulmod(r, xp.p[a.lgR + 7]) ^ wv[w];  // a wave is 2^(lgR + 7) bits
     a.partial[s] = r;
   }
 }
@@ -491,42 +423,21 @@ static_assert(kCfSliceBlock == 256, "the slice's crc split: R * 4 pieces over 25
 
 // A thread per file: fold the slices, append the filter's trailer and the type
 // byte, write the two trailers.
-__global__ __launch_bounds__(kCfSliceBlock) void cf_finish_kernel(CfDev a, XPow xp) {
+__global__ __launch_bounds__(kCfSliceBlock) void cf_finish_kernel(CfDev a, crc32c::XPow xp) {
   const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= a.tot[kTotNf]) return;
   const uint32_t s0 = a.fsl0[f], ns = a.fsl0[f + 1] - s0;
   if (ns == 0) return;  // the block is not built
   const uint32_t L = a.fL[f], R = 1u << a.lgR;
   uint32_t raw = 0;
-  for (uint32_t js = 0; js + 1 < ns; js++) raw = mulmod(raw, xp.p[a.lgR + 9]) ^ a.partial[s0 + js];  // 64 R bytes
-  raw = mulmod(raw, xpow(xp, static_cast<uint64_t>(L - (ns - 1) * R) * kLineBits)) ^ a.partial[s0 + ns - 1];
+  for (uint32_t js = 0; js + 1 < ns; js++) raw = crc32c::mulmod(raw, xp.p[a.lgR + 9]) ^ a.partial[s0 + js];  // 64 R bytes
+  raw = crc32c::mulmod(raw, crc32c::xpow(xp, static_cast<uint64_t>(L - (ns - 1) * R) * kLineBits)) ^ a.partial[s0 + ns - 1];
   uint8_t tr[10] = {static_cast<uint8_t>(static_cast<int8_t>(a.k)), static_cast<uint8_t>(L), static_cast<uint8_t>(L >> 8),
                     static_cast<uint8_t>(L >> 16), static_cast<uint8_t>(L >> 24), 0 /* kNoCompression */};
-  for (int j = 0; j < 6; j++) raw = raw_byte(raw, tr[j]);
-  const uint64_t len = 64ull * L + 6;
-  const uint32_t value = ~(mulmod(0xffffffffu, xpow(xp, len << 3)) ^ raw);
-  const uint32_t m = ((value >> 15) | (value << 17)) + 0xa282ead8u;  // crc32c::Mask
-  tr[6] = static_cast<uint8_t>(m);
-  tr[7] = static_cast<uint8_t>(m >> 8);
-  tr[8] = static_cast<uint8_t>(m >> 16);
-  tr[9] = static_cast<uint8_t>(m >> 24);
+  for (int j = 0; j < 6; j++) raw = crc32c::raw_byte(raw, tr[j]);
+  crc32c::store_trailer(tr + 5, 0, crc32c::value(raw, 64ull * L + 6, xp));
   uint8_t* out = a.filters + a.fbase[f] + 64ull * L;
   for (int j = 0; j < 10; j++) out[j] = tr[j];
-}
-
-XPow make_xpow() {
-  XPow x;
-  auto mul = [](uint32_t p, uint32_t q) {
-    uint32_t r = 0;
-    for (int i = 0; i < 32; i++) {
-      if (p & (0x80000000u >> i)) r ^= q;
-      q = (q & 1u) ? (q >> 1) ^ kPoly : (q >> 1);
-    }
-    return r;
-  };
-  x.p[0] = 0x40000000u;  // x^1
-  for (int k = 1; k < 40; k++) x.p[k] = mul(x.p[k - 1], x.p[k - 1]);
-  return x;
 }
 
 }  // namespace
@@ -535,7 +446,7 @@ hipError_t launch_compaction_filters(const CfDev& a, hipEvent_t* ev, hipStream_t
   if (a.chunks == 0 || a.slice_wgs == 0 || a.lgR < kCfMinLgR || a.lgR > kCfMaxLgR || a.bpk < 1 || a.bpk > kCfMaxBpk ||
       a.file_cap > kCoMaxFiles)
     return hipErrorInvalidValue;
-  static const XPow xp = make_xpow();
+  static const crc32c::XPow xp = crc32c::make_xpow();
   // whole words at a word stride: the hash reads its key without a shift
   const bool fixed = !a.koff;
   hipError_t e;

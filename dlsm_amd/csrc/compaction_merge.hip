@@ -54,6 +54,7 @@
 
 #include "bloom_internal.h"
 #include "sort_pass.h"
+#include "wg_scan.h"
 
 namespace dlsm {
 namespace {
@@ -72,24 +73,6 @@ struct CmAt {
   const uint64_t* p;
   __device__ uint64_t at(uint64_t i) const { return p[i]; }
 };
-
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-#pragma unroll
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
-// The sum of v over the workgroup, in every thread.  sh: kCmWaves slots.
-__device__ __forceinline__ uint64_t block_sum(uint64_t v, uint64_t* sh) {
-  v = wave_sum(v);
-  __syncthreads();  // sh may still be read from the call before
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  uint64_t t = 0;
-#pragma unroll
-  for (int w = 0; w < kCmWaves; w++) t += sh[w];
-  return t;
-}
 
 // The exclusive scans of v[0..3) over the workgroup, in place; all[q]: the
 // sums.  The waves' totals are scanned by the first wave, so a thread reads two
@@ -293,9 +276,9 @@ __global__ __launch_bounds__(kCmBlock) void cm_decide_kernel(CmDev a) {
     kb += ks;
     vb += vs;
   }
-  cnt = block_sum(cnt, sh);
-  kb = block_sum(kb, sh);
-  vb = block_sum(vb, sh);
+  cnt = block_sum<kCmWaves>(cnt, sh);
+  kb = block_sum<kCmWaves>(kb, sh);
+  vb = block_sum<kCmWaves>(vb, sh);
   if (threadIdx.x == 0) {
     a.wg_cnt[blockIdx.x] = cnt;
     a.wg_kb[blockIdx.x] = kb;
@@ -322,9 +305,9 @@ __global__ __launch_bounds__(kCmBlock) void cm_offsets_kernel(CmDev a) {
     rk += a.wg_kb[j];
     rv += a.wg_vb[j];
   }
-  rc = block_sum(rc, sh);
-  rk = block_sum(rk, sh);
-  rv = block_sum(rv, sh);
+  rc = block_sum<kCmWaves>(rc, sh);
+  rk = block_sum<kCmWaves>(rk, sh);
+  rv = block_sum<kCmWaves>(rv, sh);
   if (blockIdx.x == 0) {
     uint64_t tc = 0, tk = 0, tv = 0;
     for (uint32_t j = threadIdx.x; j < a.nwg; j += kCmBlock) {
@@ -332,9 +315,9 @@ __global__ __launch_bounds__(kCmBlock) void cm_offsets_kernel(CmDev a) {
       tk += a.wg_kb[j];
       tv += a.wg_vb[j];
     }
-    tc = block_sum(tc, sh);
-    tk = block_sum(tk, sh);
-    tv = block_sum(tv, sh);
+    tc = block_sum<kCmWaves>(tc, sh);
+    tk = block_sum<kCmWaves>(tk, sh);
+    tv = block_sum<kCmWaves>(tv, sh);
     if (threadIdx.x == 0) {
       a.wko[tc] = tk;
       a.wvo[tc] = tv;

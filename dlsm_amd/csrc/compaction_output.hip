@@ -37,12 +37,17 @@
 // kTbIndexSpan content bytes.
 //
 // Seal (co_seal_parts_kernel, co_seal_finish_kernel): crc32c of every block
-// that fits, their 32 KiB parts one flat list found through the part table the
-// region launch left; a thread per file folds its parts and writes the trailer.
+// that fits (crc32c_dev.h), their 32 KiB parts one flat list found through the
+// part table the region launch left; a thread per file folds its parts and
+// writes the trailer.
+//
+// The workgroup sums, scans and the 64-ary search are wg_scan.h's.
 #include <hip/hip_runtime.h>
 
 #include "bloom_internal.h"
+#include "crc32c_dev.h"
 #include "sort_pass.h"
+#include "wg_scan.h"
 
 namespace dlsm {
 namespace {
@@ -61,64 +66,6 @@ static_assert(kCoSealPieces % kCoSealBlock == 0, "whole passes per part");
 
 // tot[]: what the launches hand on
 enum { kTotN, kTotFlags, kTotFiles, kTotNf, kTotData, kTotRegionSpans, kTotIndexSpans, kTotParts, kTotFinal };
-
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-#pragma unroll
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
-// The sum of v over the workgroup, in every thread.  sh: kCoWaves slots.
-__device__ __forceinline__ uint64_t block_sum(uint64_t v, uint64_t* sh) {
-  v = wave_sum(v);
-  __syncthreads();  // sh may still be read from the call before
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  uint64_t t = 0;
-#pragma unroll
-  for (int w = 0; w < kCoWaves; w++) t += sh[w];
-  return t;
-}
-
-// The exclusive scan of v over the workgroup; *all: the sum.
-__device__ __forceinline__ uint64_t block_scan(uint64_t v, uint64_t* sh, uint64_t* all) {
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint64_t inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint64_t up = __shfl_up(inc, d, 64);
-    inc += lane >= static_cast<uint32_t>(d) ? up : 0;
-  }
-  __syncthreads();
-  if (lane == 63) sh[wave] = inc;
-  __syncthreads();
-  uint64_t before = 0, sum = 0;
-#pragma unroll
-  for (int w = 0; w < kCoWaves; w++) {
-    const uint64_t t = sh[w];
-    before += static_cast<uint32_t>(w) < wave ? t : 0;
-    sum += t;
-  }
-  *all = sum;
-  return before + inc - v;
-}
-
-// The last i in [0, n) with f(i) <= p, given f(0) <= p (n >= 1) and f
-// ascending: a 64-ary search, every lane of the (whole, converged) wave probing
-// one point per step.  The same answer in every lane.
-template <class F>
-__device__ __forceinline__ uint64_t wave_last_le(F f, uint64_t n, uint64_t p) {
-  const uint64_t lane = threadIdx.x & 63;
-  uint64_t lo = 0;
-  for (uint64_t len = n; len > 1;) {
-    const uint64_t step = (len + 63) >> 6;
-    const bool ok = lane * step < len && f(lo + lane * step) <= p;
-    const uint64_t k = static_cast<uint64_t>(__popcll(__ballot(ok))) - 1;  // lane 0's point is f(lo) <= p
-    lo += k * step;
-    len = len - k * step < step ? len - k * step : step;
-  }
-  return lo;
-}
 
 // The run's pair count as `merged` on the device gives it; 0 and *flagged where
 // the run is not a whole run or does not fit the grids.
@@ -143,7 +90,7 @@ __global__ __launch_bounds__(kCoBlock) void co_size_kernel(CoDev a) {
     big |= ks > 0xffffffffull || vs > 0xffffffffull || p > 0xffffffffull;
     sum += p;
   }
-  sum = block_sum(sum, sh);
+  sum = block_sum<kCoWaves>(sum, sh);
   shortk = __syncthreads_or(shortk);
   big = __syncthreads_or(big);
   if (threadIdx.x == 0) {
@@ -158,7 +105,7 @@ __global__ __launch_bounds__(kCoBlock) void co_offsets_kernel(CoDev a) {
   const uint64_t n = co_pairs(a, &flagged);
   uint64_t below = 0;
   for (uint32_t j = threadIdx.x; j < blockIdx.x; j += kCoBlock) below += a.wg_sum[j];
-  uint64_t run = block_sum(below, sh);
+  uint64_t run = block_sum<kCoWaves>(below, sh);
   if (blockIdx.x == 0) {
     uint64_t total = 0;
     int shortk = 0, big = 0;
@@ -167,7 +114,7 @@ __global__ __launch_bounds__(kCoBlock) void co_offsets_kernel(CoDev a) {
       shortk |= (a.wg_flags[j] & kTbShortKey) != 0;
       big |= (a.wg_flags[j] & kTbPairTooBig) != 0;
     }
-    total = block_sum(total, sh);
+    total = block_sum<kCoWaves>(total, sh);
     shortk = __syncthreads_or(shortk);
     big = __syncthreads_or(big);
     if (threadIdx.x == 0) {
@@ -182,7 +129,7 @@ __global__ __launch_bounds__(kCoBlock) void co_offsets_kernel(CoDev a) {
     const uint64_t i = c * kTbChunk + threadIdx.x;
     const uint64_t p = i < n ? tb_pair_size(a.src.key_size(i), a.src.value_size(i)) : 0;
     uint64_t all;
-    const uint64_t o = run + block_scan(p, sh, &all);
+    const uint64_t o = run + block_scan<uint64_t, kCoWaves>(p, sh, &all);
     if (i < n) a.off[i] = o;
     run += all;
   }
@@ -225,9 +172,9 @@ __global__ __launch_bounds__(kCoBlock) void co_cut_kernel(CoDev a) {
     const uint32_t f = f0 + threadIdx.x;
     const uint64_t bytes = f < nf ? off[scut[f + 1]] - off[scut[f]] : 0;
     uint64_t dall, sall;
-    const uint64_t base = drun + block_scan(co_pad16(bytes), sh, &dall);
+    const uint64_t base = drun + block_scan<uint64_t, kCoWaves>(co_pad16(bytes), sh, &dall);
     const uint64_t lim = bytes < co_left(a.data_cap, base) ? bytes : co_left(a.data_cap, base);
-    const uint64_t sp = srun + block_scan((lim + kTbSpan - 1) / kTbSpan, sh, &sall);
+    const uint64_t sp = srun + block_scan<uint64_t, kCoWaves>((lim + kTbSpan - 1) / kTbSpan, sh, &sall);
     if (f < nf) {
       a.cut[f] = scut[f];
       a.data_base[f] = base;
@@ -307,7 +254,7 @@ __global__ __launch_bounds__(kCoBlock) void co_entries_kernel(CoDev a) {
       e = tb_entry_len(a.src.key_size(i), o - ob, off[i + 1] - o);
     }
     uint64_t eall;
-    const uint64_t r = erun + block_scan(e, sh, &eall);
+    const uint64_t r = erun + block_scan<uint64_t, kCoWaves>(e, sh, &eall);
     if (i < n) a.erel[i] = r;
     erun += eall;
   }
@@ -318,7 +265,7 @@ __global__ __launch_bounds__(kCoBlock) void co_entries_kernel(CoDev a) {
 // sum of all in every thread.
 __device__ __forceinline__ uint64_t co_stage_esum(const CoDev& a, uint64_t* swg, uint64_t* sh) {
   uint64_t all;
-  const uint64_t x = block_scan(threadIdx.x < a.nwg ? a.wg_esum[threadIdx.x] : 0, sh, &all);
+  const uint64_t x = block_scan<uint64_t, kCoWaves>(threadIdx.x < a.nwg ? a.wg_esum[threadIdx.x] : 0, sh, &all);
   if (threadIdx.x < a.nwg) swg[threadIdx.x] = x;
   __syncthreads();
   return all;
@@ -343,12 +290,12 @@ __device__ __forceinline__ void co_finish(const CoDev& a, uint64_t* sh, uint32_t
     const uint64_t E = in ? G(e) - G(b) : 0, ctot = E + 4 * fn + 4, ib = ctot + 5;
     const uint64_t nch = in ? a.nch[f] : 0;
     uint64_t iall, call, sall, pall;
-    const uint64_t ibase = irun + block_scan(in ? co_pad16(ib) : 0, sh, &iall);
-    const uint64_t cbase = crun + block_scan(nch, sh, &call);
+    const uint64_t ibase = irun + block_scan<uint64_t, kCoWaves>(in ? co_pad16(ib) : 0, sh, &iall);
+    const uint64_t cbase = crun + block_scan<uint64_t, kCoWaves>(nch, sh, &call);
     const uint64_t left = co_left(a.index_cap, ibase), lim = ctot < left ? ctot : left;
     const bool fits = in && ib <= left;
-    const uint64_t sp = srun + block_scan(in ? (lim + kTbIndexSpan - 1) / kTbIndexSpan : 0, sh, &sall);
-    const uint64_t pt = prun + block_scan(fits ? co_seal_parts(ctot) : 0, sh, &pall);
+    const uint64_t sp = srun + block_scan<uint64_t, kCoWaves>(in ? (lim + kTbIndexSpan - 1) / kTbIndexSpan : 0, sh, &sall);
+    const uint64_t pt = prun + block_scan<uint64_t, kCoWaves>(fits ? co_seal_parts(ctot) : 0, sh, &pall);
     if (in) {
       const uint32_t ff = a.fflag[f];
       toobig |= ctot > 0xffffffffull;
@@ -563,39 +510,10 @@ __global__ __launch_bounds__(kCoBlock) void co_index_kernel(CoDev a) {
   }
 }
 
-// ---- the seal: crc32c (Castagnoli), the algebra of block_crc.hip ---------------
-constexpr uint32_t kPoly = 0x82f63b78u;  // reflected
-
-// a(x) * b(x) mod P in the reflected representation (bit 31 = x^0).
-__device__ __forceinline__ uint32_t mulmod(uint32_t x, uint32_t y) {
-  uint32_t p = 0;
-#pragma unroll
-  for (int i = 0; i < 32; i++) {
-    if (x & (0x80000000u >> i)) p ^= y;
-    y = (y & 1u) ? (y >> 1) ^ kPoly : (y >> 1);
-  }
-  return p;
-}
-
-struct XPow {
-  uint32_t p[40];  // x^(2^k) mod P
-};
-
-__device__ __forceinline__ uint32_t raw_byte(uint32_t r, uint32_t x) {
-  r ^= x;
-#pragma unroll
-  for (int k = 0; k < 8; k++) r = (r & 1u) ? (r >> 1) ^ kPoly : (r >> 1);
-  return r;
-}
-
-__device__ __forceinline__ uint32_t raw_word(uint32_t r, uint32_t w, const uint32_t* T) {
-  r ^= w;
-  return T[768 + (r & 0xffu)] ^ T[512 + ((r >> 8) & 0xffu)] ^ T[256 + ((r >> 16) & 0xffu)] ^ T[r >> 24];
-}
-
+// ---- the seal --------------------------------------------------------------
 // Part g of the flat list: the raw crc of kCoSealPieces 16-byte pieces of one
 // block's contents, zero pieces in front of a block's first part.
-__global__ __launch_bounds__(kCoSealBlock) void co_seal_parts_kernel(CoDev a, XPow xp) {
+__global__ __launch_bounds__(kCoSealBlock) void co_seal_parts_kernel(CoDev a, crc32c::XPow xp) {
   __shared__ uint32_t T[1024];
   __shared__ uint32_t wv[kCoSealBlock / 64];
   const uint32_t g = blockIdx.x;
@@ -607,9 +525,9 @@ __global__ __launch_bounds__(kCoSealBlock) void co_seal_parts_kernel(CoDev a, XP
   const int64_t pieces = static_cast<int64_t>(ctot / 16);
   const int64_t lead = static_cast<int64_t>(co_seal_parts(ctot)) * kCoSealPieces - pieces;
   const uint8_t* src = a.index + a.index_base[f];
-  {  // the slice-by-4 tables
+  {  // the slice-by-4 tables (the header's table build, written out like the fold below)
     uint32_t c = threadIdx.x;
-    for (int k = 0; k < 8; k++) c = (c & 1u) ? (c >> 1) ^ kPoly : (c >> 1);
+    for (int k = 0; k < 8; k++) c = (c & 1u) ? (c >> 1) ^ crc32c::kPoly : (c >> 1);
     T[threadIdx.x] = c;
     __syncthreads();
     for (int t = 1; t < 4; t++) {
@@ -624,26 +542,28 @@ __global__ __launch_bounds__(kCoSealBlock) void co_seal_parts_kernel(CoDev a, XP
     const int64_t q = static_cast<int64_t>(part) * kCoSealPieces + i * kCoSealBlock + threadIdx.x - lead;
     v[i] = q < 0 ? make_uint4(0, 0, 0, 0) : *reinterpret_cast<const uint4*>(src + 16 * q);  // q < pieces
   }
+  // crc32c::part_fold, written out: through the shared functions the seal of a
+  // hundred files measured one percent slower (crc32c_dev.h)
   uint32_t acc = 0;
 #pragma unroll
   for (int i = 0; i < kCoSealPasses; i++) {
-    uint32_t r = raw_word(0, v[i].x, T);
-    r = raw_word(r, v[i].y, T);
-    r = raw_word(r, v[i].z, T);
-    r = raw_word(r, v[i].w, T);
-    acc = mulmod(acc, xp.p[15]) ^ r;  // a pass is 4 KiB = 2^15 bits
+    uint32_t r = crc32c::raw_word(0, v[i].x, T);
+    r = crc32c::raw_word(r, v[i].y, T);
+    r = crc32c::raw_word(r, v[i].z, T);
+    r = crc32c::raw_word(r, v[i].w, T);
+    acc = crc32c::mulmod(acc, xp.p[15]) ^ r;  // a pass is 4 KiB = 2^15 bits
   }
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < 6; k++) {  // level k joins neighbours of 16 * 2^k bytes
     const uint32_t other = __shfl_xor(acc, 1 << k, 64);
-    if ((lane & (1 << k)) == 0) acc = mulmod(acc, xp.p[k + 7]) ^ other;
+    if ((lane & (1 << k)) == 0) acc = crc32c::mulmod(acc, xp.p[k + 7]) ^ other;
   }
   if (lane == 0) wv[w] = acc;
   __syncthreads();
   if (threadIdx.x == 0) {
     uint32_t s = 0;
-    for (int q2 = 0; q2 < kCoSealBlock / 64; q2++) s = mulmod(s, xp.p[13]) ^ wv[q2];  // a wave is 1 KiB
+    for (int q2 = 0; q2 < kCoSealBlock / 64; q2++) s = crc32c::mulmod(s, xp.p[13]) ^ wv[q2];  // a wave is 1 KiB
     a.partial[g] = s;
   }
 }
@@ -651,22 +571,22 @@ static_assert(kCoSealBlock == 256 && kCoSealPasses * kCoSealBlock * 16 == 32768,
 
 // A thread per file: fold the parts, append the bytes behind the last piece and
 // the type byte, write the trailer.
-__global__ void co_seal_finish_kernel(CoDev a, XPow xp) {
+__global__ void co_seal_finish_kernel(CoDev a, crc32c::XPow xp) {
   const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
   if (a.tot[kTotParts] == 0 || f >= a.tot[kTotNf]) return;
   const uint64_t ctot = a.seal_len[f];
   if (ctot == 0) return;  // the block does not fit: no trailer
   uint8_t* blk = a.index + a.index_base[f];
   uint32_t raw = 0;
-  for (uint32_t p = a.part0[f]; p < a.part0[f + 1]; p++) raw = mulmod(raw, xp.p[18]) ^ a.partial[p];  // 32 KiB
-  for (uint64_t d = ctot / 16 * 16; d < ctot; d++) raw = raw_byte(raw, blk[d]);
-  raw = raw_byte(raw, 0);  // kNoCompression
+  for (uint32_t p = a.part0[f]; p < a.part0[f + 1]; p++) raw = crc32c::mulmod(raw, xp.p[18]) ^ a.partial[p];  // 32 KiB
+  for (uint64_t d = ctot / 16 * 16; d < ctot; d++) raw = crc32c::raw_byte(raw, blk[d]);
+  raw = crc32c::raw_byte(raw, 0);  // kNoCompression
+  // crc32c::value and store_trailer, written out as the parts kernel's fold is
   uint32_t xn = 0x80000000u;  // x^(8 (ctot + 1))
   uint64_t bits = (ctot + 1) << 3;
   for (int k = 0; bits; k++, bits >>= 1)
-    if (bits & 1u) xn = mulmod(xn, xp.p[k]);
-  const uint32_t value = ~(mulmod(0xffffffffu, xn) ^ raw);
-  const uint32_t m = ((value >> 15) | (value << 17)) + 0xa282ead8u;  // crc32c::Mask
+    if (bits & 1u) xn = crc32c::mulmod(xn, xp.p[k]);
+  const uint32_t m = crc32c::mask(~(crc32c::mulmod(0xffffffffu, xn) ^ raw));
   blk[ctot] = 0;
   blk[ctot + 1] = static_cast<uint8_t>(m);
   blk[ctot + 2] = static_cast<uint8_t>(m >> 8);
@@ -674,27 +594,12 @@ __global__ void co_seal_finish_kernel(CoDev a, XPow xp) {
   blk[ctot + 4] = static_cast<uint8_t>(m >> 24);
 }
 
-XPow make_xpow() {
-  XPow x;
-  auto mul = [](uint32_t p, uint32_t q) {
-    uint32_t r = 0;
-    for (int i = 0; i < 32; i++) {
-      if (p & (0x80000000u >> i)) r ^= q;
-      q = (q & 1u) ? (q >> 1) ^ kPoly : (q >> 1);
-    }
-    return r;
-  };
-  x.p[0] = 0x40000000u;  // x^1
-  for (int k = 1; k < 40; k++) x.p[k] = mul(x.p[k - 1], x.p[k - 1]);
-  return x;
-}
-
 }  // namespace
 
 hipError_t launch_compaction_output(const CoDev& a, uint32_t index_wgs, uint32_t seal_wgs, hipEvent_t* ev, hipStream_t s) {
   if (a.nwg == 0 || a.nwg > kSortMaxWgs || a.cpw == 0 || a.copy_wgs == 0 || index_wgs == 0 || seal_wgs == 0)
     return hipErrorInvalidValue;
-  static const XPow xp = make_xpow();
+  static const crc32c::XPow xp = crc32c::make_xpow();
   const bool fixed = !a.src.koff && !a.src.voff;
   hipError_t e;
   auto mark = [&](int j) { return ev ? hipEventRecord(ev[j], s) : hipSuccess; };

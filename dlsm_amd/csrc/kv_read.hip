@@ -33,6 +33,7 @@
 
 #include "bloom_internal.h"
 #include "sort_pass.h"
+#include "wg_scan.h"
 
 namespace dlsm {
 namespace {
@@ -47,24 +48,6 @@ constexpr int kKvUnits = kKvSpan / (16 * kKvBlock);  // units per lane and span
 __device__ __forceinline__ uint64_t kv_item_count(const KvReadDev& a) {
   const uint64_t c = a.count ? *a.count : a.cap;
   return c < a.cap ? c : a.cap;
-}
-
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-#pragma unroll
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
-// The sum of v over the workgroup, in every thread.  sh: kKvWaves slots.
-__device__ __forceinline__ uint64_t block_sum(uint64_t v, uint64_t* sh) {
-  v = wave_sum(v);
-  __syncthreads();  // sh may still be read from the call before
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  uint64_t t = 0;
-#pragma unroll
-  for (int w = 0; w < kKvWaves; w++) t += sh[w];
-  return t;
 }
 
 __global__ __launch_bounds__(kKvBlock) void kv_size_kernel(KvReadDev a) {
@@ -100,8 +83,8 @@ __global__ __launch_bounds__(kKvBlock) void kv_size_kernel(KvReadDev a) {
     a.src[i] = reinterpret_cast<uint64_t>(value);
     sum += len;
   }
-  sum = block_sum(sum, sh);
-  bad = block_sum(bad, sh);
+  sum = block_sum<kKvWaves>(sum, sh);
+  bad = block_sum<kKvWaves>(bad, sh);
   if (threadIdx.x == 0) {
     a.wg_sum[blockIdx.x] = sum;
     a.wg_bad[blockIdx.x] = bad;
@@ -114,11 +97,11 @@ __global__ __launch_bounds__(kKvBlock) void kv_offsets_kernel(KvReadDev a) {
   // the exclusive scan of the workgroup sums, this workgroup's entry of it
   uint64_t below = 0;
   for (uint32_t j = threadIdx.x; j < blockIdx.x; j += kKvBlock) below += a.wg_sum[j];
-  uint64_t run = block_sum(below, sh);
+  uint64_t run = block_sum<kKvWaves>(below, sh);
   if (blockIdx.x == 0) {
     uint64_t bad = 0;
     for (uint32_t j = threadIdx.x; j < a.nwg; j += kKvBlock) bad += a.wg_bad[j];
-    bad = block_sum(bad, sh);
+    bad = block_sum<kKvWaves>(bad, sh);
     if (threadIdx.x == 0) {
       if (a.n_corrupt) *a.n_corrupt = bad;
       if (m == 0) a.value_off[0] = 0;

@@ -43,6 +43,7 @@
 
 #include "bloom_internal.h"
 #include "sort_pass.h"
+#include "wg_scan.h"
 
 namespace dlsm {
 namespace {
@@ -54,64 +55,6 @@ static_assert(kTbWindow + 1 == kTbBlock, "a thread stages one offset of the wind
 static_assert(kTbSpan % (16 * kTbBlock) == 0, "every lane owns the same number of units of a span");
 static_assert(kTbIndexSpan / 16 <= kTbBlock && kTbIndexWindow <= kTbBlock, "a thread per unit and per entry of an index span");
 constexpr int kTbUnits = kTbSpan / (16 * kTbBlock);  // units per lane and span
-
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-#pragma unroll
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
-// The sum of v over the workgroup, in every thread.  sh: kTbWaves slots.
-__device__ __forceinline__ uint64_t block_sum(uint64_t v, uint64_t* sh) {
-  v = wave_sum(v);
-  __syncthreads();  // sh may still be read from the call before
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  uint64_t t = 0;
-#pragma unroll
-  for (int w = 0; w < kTbWaves; w++) t += sh[w];
-  return t;
-}
-
-// The exclusive scan of v over the workgroup; *all: the sum.
-__device__ __forceinline__ uint64_t block_scan(uint64_t v, uint64_t* sh, uint64_t* all) {
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint64_t inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint64_t up = __shfl_up(inc, d, 64);
-    inc += lane >= static_cast<uint32_t>(d) ? up : 0;
-  }
-  __syncthreads();
-  if (lane == 63) sh[wave] = inc;
-  __syncthreads();
-  uint64_t before = 0, sum = 0;
-#pragma unroll
-  for (int w = 0; w < kTbWaves; w++) {
-    const uint64_t t = sh[w];
-    before += static_cast<uint32_t>(w) < wave ? t : 0;
-    sum += t;
-  }
-  *all = sum;
-  return before + inc - v;
-}
-
-// The last i in [0, n) with f(i) <= p, given f(0) <= p (n >= 1) and f
-// ascending: a 64-ary search, every lane of the (whole, converged) wave probing
-// one point per step.  The same answer in every lane.
-template <class F>
-__device__ __forceinline__ uint64_t wave_last_le(F f, uint64_t n, uint64_t p) {
-  const uint64_t lane = threadIdx.x & 63;
-  uint64_t lo = 0;
-  for (uint64_t len = n; len > 1;) {
-    const uint64_t step = (len + 63) >> 6;
-    const bool ok = lane * step < len && f(lo + lane * step) <= p;
-    const uint64_t k = static_cast<uint64_t>(__popcll(__ballot(ok))) - 1;  // lane 0's point is f(lo) <= p
-    lo += k * step;
-    len = len - k * step < step ? len - k * step : step;
-  }
-  return lo;
-}
 
 __global__ __launch_bounds__(kTbBlock) void tb_size_kernel(TbDev a) {
   __shared__ uint64_t sh[kTbWaves];
@@ -126,7 +69,7 @@ __global__ __launch_bounds__(kTbBlock) void tb_size_kernel(TbDev a) {
     big |= ks > 0xffffffffull || vs > 0xffffffffull || p > 0xffffffffull;
     sum += p;
   }
-  sum = block_sum(sum, sh);
+  sum = block_sum<kTbWaves>(sum, sh);
   shortk = __syncthreads_or(shortk);
   big = __syncthreads_or(big);
   if (threadIdx.x == 0) {
@@ -139,7 +82,7 @@ __global__ __launch_bounds__(kTbBlock) void tb_offsets_kernel(TbDev a) {
   __shared__ uint64_t sh[kTbWaves];
   uint64_t below = 0;
   for (uint32_t j = threadIdx.x; j < blockIdx.x; j += kTbBlock) below += a.wg_sum[j];
-  uint64_t run = block_sum(below, sh);
+  uint64_t run = block_sum<kTbWaves>(below, sh);
   if (blockIdx.x == 0) {
     uint64_t total = 0;
     int shortk = 0, big = 0;
@@ -148,7 +91,7 @@ __global__ __launch_bounds__(kTbBlock) void tb_offsets_kernel(TbDev a) {
       shortk |= (a.wg_flags[j] & kTbShortKey) != 0;
       big |= (a.wg_flags[j] & kTbPairTooBig) != 0;
     }
-    total = block_sum(total, sh);
+    total = block_sum<kTbWaves>(total, sh);
     shortk = __syncthreads_or(shortk);
     big = __syncthreads_or(big);
     if (threadIdx.x == 0) {
@@ -166,9 +109,9 @@ __global__ __launch_bounds__(kTbBlock) void tb_offsets_kernel(TbDev a) {
     const bool in = i < a.n;
     const uint64_t ks = in ? a.src.key_size(i) : 0, p = in ? tb_pair_size(ks, a.src.value_size(i)) : 0;
     uint64_t all, eall;
-    const uint64_t o = run + block_scan(p, sh, &all);
+    const uint64_t o = run + block_scan<uint64_t, kTbWaves>(p, sh, &all);
     const uint64_t e = in ? tb_entry_len(ks, o, p) : 0;
-    const uint64_t r = erun + block_scan(e, sh, &eall);
+    const uint64_t r = erun + block_scan<uint64_t, kTbWaves>(e, sh, &eall);
     if (in) {
       a.off[i] = o;
       a.erel[i] = r;
@@ -183,7 +126,7 @@ __global__ __launch_bounds__(kTbBlock) void tb_offsets_kernel(TbDev a) {
 __device__ __forceinline__ void tb_finish(const TbDev& a, uint64_t* sh) {
   uint64_t E = 0;
   for (uint32_t j = threadIdx.x; j < a.nwg; j += kTbBlock) E += a.wg_esum[j];
-  E = block_sum(E, sh);
+  E = block_sum<kTbWaves>(E, sh);
   if (threadIdx.x >= 64) return;  // one wave walks the chain
   const bool lane0 = threadIdx.x == 0;
   const uint64_t n = a.n, total = a.built[0];
@@ -225,7 +168,7 @@ __device__ __forceinline__ void tb_finish(const TbDev& a, uint64_t* sh) {
 __device__ __forceinline__ void tb_starts(const TbDev& a, uint32_t w, uint64_t* sh) {
   uint64_t below = 0;
   for (uint32_t j = threadIdx.x; j < w; j += kTbBlock) below += a.wg_esum[j];
-  const uint64_t base = block_sum(below, sh);
+  const uint64_t base = block_sum<kTbWaves>(below, sh);
   const uint64_t c0 = static_cast<uint64_t>(w) * a.cpw;
   for (uint64_t c = c0; c < c0 + a.cpw; c++) {
     const uint64_t i = c * kTbChunk + threadIdx.x;

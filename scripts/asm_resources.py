@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Compare two `make asm` outputs kernel by kernel.
 
-    scripts/asm_resources.py BEFORE_DIR AFTER_DIR [--map OLD_REGEX=NEW ...]
+    scripts/asm_resources.py BEFORE_DIR AFTER_DIR [--stem FILE_STEM] [--map OLD_REGEX=NEW ...]
 
-Each directory holds resource_usage.txt and bloom_kernels.s.  Kernels are keyed
+Each directory holds what `make asm ASM=FILE_STEM` left: FILE_STEM.s and
+FILE_STEM.resource_usage.txt (resource_usage.txt for the default stem,
+bloom_kernels).  Kernels are keyed
 by demangled name (source locations dropped); --map rewrites a BEFORE name
 (re.sub) so that a kernel whose signature changed lines up with its successor.
 Prints the kernels only one side has, every resource difference, and every
@@ -57,16 +59,19 @@ def bodies(path, wanted):
 
 
 def main():
-    argv, args, maps = sys.argv[1:], [], []
+    argv, args, maps, stem = sys.argv[1:], [], [], "bloom_kernels"
     while argv:
         a = argv.pop(0)
         if a == "--map":
             old, _, new = argv.pop(0).partition("=")
             maps.append((re.compile(old), new))
+        elif a == "--stem":
+            stem = argv.pop(0)
         else:
             args.append(a)
     before_dir, after_dir = args
-    rb, ra = resources(before_dir + "/resource_usage.txt"), resources(after_dir + "/resource_usage.txt")
+    usage = "/resource_usage.txt" if stem == "bloom_kernels" else f"/{stem}.resource_usage.txt"
+    rb, ra = resources(before_dir + usage), resources(after_dir + usage)
     db, da = demangle(list(rb)), demangle(list(ra))
     mapped = {}  # demangled-before -> (renamed, mangled)
     for mangled, name in db.items():
@@ -95,8 +100,8 @@ def main():
                     print(f"    {f}: {b.get(f)} -> {a.get(f)}")
         renamed[old_m] = after[name]
     print(f"resources identical: {same}, different: {diff}")
-    tb = bodies(before_dir + "/bloom_kernels.s", set(renamed))
-    ta = bodies(after_dir + "/bloom_kernels.s", set(renamed.values()))
+    tb = bodies(before_dir + f"/{stem}.s", set(renamed))
+    ta = bodies(after_dir + f"/{stem}.s", set(renamed.values()))
     isa_same = 0
     for old_m, new_m in sorted(renamed.items(), key=lambda kv: da[kv[1]]):
         x, y = tb[old_m], ta[new_m]
