@@ -36,7 +36,7 @@ __all__ = [
     "TableData", "kv_read_chunk", "kv_read_span", "kv_pair_read",
     "table_build", "table_build_chunk", "table_build_span", "table_build_bound",
     "compaction_merge", "merge_tile", "merge_span", "merge_chunk", "MERGE_KEEP_ALL", "MERGE_DROP_HIDDEN",
-    "compaction_merge_tables", "MERGE_TABLE_MISMATCH",
+    "compaction_merge_tables", "MERGE_TABLE_MISMATCH", "memtable_sort", "sort_tile",
     "compaction_output", "compaction_output_bound", "output_tables", "OUTPUT_FILE_FIELDS", "OUTPUT_MAX_FILES", "OUTPUT_FILE_CAP", "OUTPUT_INPUT_FLAGGED",
     "compaction_filters", "compaction_filters_bound", "filter_blocks", "FILTER_REC_FIELDS", "FILTERS_MAX_SLICES", "FILTERS_CAP",
     "FILTERS_TOO_MANY_LINES", "FILTERS_INPUT_FLAGGED",
@@ -289,6 +289,26 @@ def compaction_merge(runs, policy: int = MERGE_DROP_HIDDEN, smallest_snapshot: i
     key_off uint64, values uint8, value_off uint64, src uint64, merged) with
     merged = (n_in, n_out, key_bytes, value_bytes, flags); the arrays are cut at
     min(total, cap).  The caps default to what the inputs hold."""
+    return _merge_host(runs, policy, smallest_snapshot, keys_cap, values_cap, pair_cap, ctx, False)
+
+
+def sort_tile() -> int:
+    """Records one workgroup of the memtable sort sorts in LDS."""
+    return int(lib().dlsm_memtable_sort_tile())
+
+
+def memtable_sort(batch, policy: int = MERGE_DROP_HIDDEN, smallest_snapshot: int = 0, *,
+                  keys_cap: Optional[int] = None, values_cap: Optional[int] = None, pair_cap: Optional[int] = None,
+                  ctx: Optional["Context"] = None):
+    """The host form of the memtable sort (dlsm_memtable_sort; no device is
+    touched): ``batch`` is one (Keys, values, value_off or None, value_len)
+    over host arrays, in arrival order.  Returns what compaction_merge returns,
+    the pairs in InternalKeyComparator order and src the input index of each."""
+    return _merge_host([batch], policy, smallest_snapshot, keys_cap, values_cap, pair_cap, ctx, True)
+
+
+def _merge_host(runs, policy, smallest_snapshot, keys_cap, values_cap, pair_cap, ctx, sort):
+    """compaction_merge, or memtable_sort of the one run."""
     def nb(x, off, n, ln):
         return int(off[n] - off[0]) if off is not None else n * ln
 
@@ -302,8 +322,11 @@ def compaction_merge(runs, policy: int = MERGE_DROP_HIDDEN, smallest_snapshot: i
     key_off, value_off = np.zeros(pair_cap + 1, dtype=np.uint64), np.zeros(pair_cap + 1, dtype=np.uint64)
     src, merged = np.zeros(max(pair_cap, 1), dtype=np.uint64), np.zeros(5, dtype=np.uint64)
     mr, mo = _merge_io(runs, keys, keys_cap, key_off, values, values_cap, value_off, src, pair_cap, merged)
-    check(lib().dlsm_compaction_merge(ctx.h if ctx is not None else None, mr, len(runs), policy, smallest_snapshot,
-                                      C.byref(mo)), "compaction_merge")
+    h = ctx.h if ctx is not None else None
+    if sort:
+        check(lib().dlsm_memtable_sort(h, mr, policy, smallest_snapshot, C.byref(mo)), "memtable_sort")
+    else:
+        check(lib().dlsm_compaction_merge(h, mr, len(runs), policy, smallest_snapshot, C.byref(mo)), "compaction_merge")
     m = tuple(int(x) for x in merged)
     p = min(m[1], pair_cap)
     return (keys[:min(m[2], keys_cap)], key_off[:p + 1], values[:min(m[3], values_cap)], value_off[:p + 1], src[:p], m)
@@ -1327,6 +1350,23 @@ class Context:
         check(lib().dlsm_compaction_merge_dev(self.h, mr, len(runs), policy, smallest_snapshot, C.byref(mo)),
               "compaction_merge_dev")
 
+    # -- memtable sort: an unsorted batch into a sorted run --------------------------
+    def memtable_sort_dev(self, batch, keys, key_off, values, value_off, merged, *, src=None,
+                          policy: int = MERGE_DROP_HIDDEN, smallest_snapshot: int = 0,
+                          keys_cap: Optional[int] = None, values_cap: Optional[int] = None,
+                          pair_cap: Optional[int] = None):
+        """Sort one batch of pairs in arrival order on the device: ``batch`` is
+        one (Keys, values, value_off or None, value_len) over device tensors.
+        The outputs are compaction_merge_dev's -- the table build's input form
+        -- with src the input index of each output pair.  Asynchronous;
+        compaction_merge_stats reports it."""
+        mr, mo = _merge_io([batch], keys, keys_cap, key_off, values, values_cap, value_off, src, pair_cap, merged)
+        check(lib().dlsm_memtable_sort_dev(self.h, mr, policy, smallest_snapshot, C.byref(mo)), "memtable_sort_dev")
+
+    def memtable_sort(self, batch, policy: int = MERGE_DROP_HIDDEN, smallest_snapshot: int = 0, **kw):
+        """The host-memory form (see dlsm_amd.memtable_sort)."""
+        return memtable_sort(batch, policy, smallest_snapshot, ctx=self, **kw)
+
     # -- compaction output: a merged run cut into size-capped tables ---------------
     def compaction_output_dev(self, keys: Keys, values, merged, data, index, chunk_end, files, built, *, value_off=None,
                               value_len: int = 0, max_file_bytes: int = 0, chunk_bytes: int = 0,
@@ -1408,8 +1448,9 @@ class Context:
 
     def compaction_merge_stats(self):
         """(record, partition, merge, decide, offsets, gather) device
-        milliseconds of the last compaction_merge_dev or
-        compaction_merge_tables_dev (call after sync) and its number of merge
+        milliseconds of the last compaction_merge_dev,
+        compaction_merge_tables_dev or memtable_sort_dev (the tile sort in the
+        record slot; call after sync) and its number of merge
         passes."""
         ms, passes = (C.c_double * 6)(), C.c_uint32()
         check(lib().dlsm_compaction_merge_stats(self.h, ms, C.byref(passes)), "compaction_merge_stats")

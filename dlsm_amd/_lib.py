@@ -261,6 +261,11 @@ SIGNATURES = [
     ("dlsm_compaction_merge_tables", C.c_int, [_VP, C.POINTER(_VP), _U64P, C.POINTER(dlsm_data_chunk),
                                                C.POINTER(C.c_uint32), C.c_int, C.POINTER(dlsm_table_run), C.c_int, C.c_int,
                                                C.c_uint64, C.POINTER(dlsm_merge_output)]),
+    ("dlsm_memtable_sort_dev", C.c_int, [_VP, C.POINTER(dlsm_merge_run), C.c_int, C.c_uint64,
+                                         C.POINTER(dlsm_merge_output)]),
+    ("dlsm_memtable_sort", C.c_int, [_VP, C.POINTER(dlsm_merge_run), C.c_int, C.c_uint64,
+                                     C.POINTER(dlsm_merge_output)]),
+    ("dlsm_memtable_sort_tile", C.c_uint32, []),
     ("dlsm_merge_tile", C.c_uint32, []),
     ("dlsm_merge_span", C.c_uint32, []),
     ("dlsm_merge_chunk", C.c_uint32, []),

@@ -176,7 +176,7 @@ struct dlsm_ctx {
   int cf_lgR = 0;            // ... its slice geometry
   uint32_t cf_slice_wgs = 0;  // ... and its slice grid
   DevBuf<uint8_t> cm_ws;      // compaction merge: table, records, offsets, partial sums (plan::CompactionMergePlan's layout)
-  hipEvent_t ev_cm[2 * kCmMaxPasses + 5] = {};  // compaction merge: around every launch (dlsm_compaction_merge_stats)
+  hipEvent_t ev_cm[2 * kMsMaxPasses + 5] = {};  // compaction merge and memtable sort: around every launch (dlsm_compaction_merge_stats)
   uint32_t cm_passes = 0;     // ... the last call's merge passes
   bool cm_timed = false;      // ... which recorded all of its events
   int cus = 0;               // the device's compute units (0: not asked yet)
@@ -3655,13 +3655,15 @@ static bool merge_output_aligned(const dlsm_merge_output* out) {
          aligned(out->src, 8) && aligned(out->merged, 8);
 }
 
-// The device half of both merge calls: the workspace, the tables' upload and
-// the launches.  tables: the runs are files of the opened tables ti / td -- P
-// is then that CompactionTablesPlan, and its runs' descriptor arrays are filled
-// in here, where the workspace is known.
+// The device half of both merge calls and of the memtable sort: the workspace,
+// the tables' upload and the launches.  tables: the runs are files of the
+// opened tables ti / td -- P is then that CompactionTablesPlan, and its runs'
+// descriptor arrays are filled in here, where the workspace is known.  sort: P
+// is that MemtableSortPlan, and the batch is sorted instead of runs merged.
 static int compaction_merge_launch(dlsm_ctx* ctx, CompactionMergePlan& P, int policy, uint64_t smallest_snapshot,
                                    const dlsm_merge_output* out, const CompactionTablesPlan* tables,
-                                   const dlsm_tableindex* ti, const dlsm_tabledata* td) {
+                                   const dlsm_tableindex* ti, const dlsm_tabledata* td,
+                                   const MemtableSortPlan* sort = nullptr) {
   DeviceGuard g(ctx->device);
   if (!ctx->cus) {
     int cus = 0;
@@ -3690,7 +3692,7 @@ static int compaction_merge_launch(dlsm_ctx* ctx, CompactionMergePlan& P, int po
   a.tab = reinterpret_cast<const CmTable*>(ws + P.tab_off);
   a.n = P.n;
   a.n_runs = P.tab.n_runs;
-  a.n_passes = P.tab.n_passes;
+  a.n_passes = sort ? sort->passes : P.tab.n_passes;
   a.policy = policy;
   a.snapshot = smallest_snapshot;
   a.rec[0] = reinterpret_cast<CmRec*>(ws + P.rec_off[0]);
@@ -3715,8 +3717,9 @@ static int compaction_merge_launch(dlsm_ctx* ctx, CompactionMergePlan& P, int po
   a.cpw = P.cpw;
   a.nwg = P.nwg;
   a.copy_wgs = plan_table_build_wgs(static_cast<uint32_t>(ctx->cus));
-  DLSM_TRY(launch_compaction_merge(a, P.tab.tiles, ctx->ev_cm, ctx->stream, tables ? &t : nullptr));
-  ctx->cm_passes = P.tab.n_passes;
+  if (sort) DLSM_TRY(launch_memtable_sort(a, ctx->ev_cm, ctx->stream));
+  else DLSM_TRY(launch_compaction_merge(a, P.tab.tiles, ctx->ev_cm, ctx->stream, tables ? &t : nullptr));
+  ctx->cm_passes = a.n_passes;
   ctx->cm_timed = true;
   return DLSM_OK;
 }
@@ -3861,6 +3864,54 @@ int dlsm_compaction_merge(dlsm_ctx* ctx, const dlsm_merge_run* runs, int n_runs,
       else if (prev_ok && cm_rec_cmp(buf[0][T.base[r] + i - 1], cur, T.runs) >= 0) flags |= kCmUnsorted;
     }
   }
+  return compaction_merge_host<false>(P, buf, flags, policy, smallest_snapshot, out);
+}
+
+// ---------------------------------------------------------------------------
+// Memtable sort: one batch in arrival order into a sorted run
+// (InternalKeyComparator, db/dbformat.cc:41-57; memtable_sort.hip)
+// ---------------------------------------------------------------------------
+uint32_t dlsm_memtable_sort_tile(void) { return kMsTile; }
+
+// The merge's argument rules over the one batch, and the sort's plan with the
+// batch as run 0.
+static int memtable_sort_plan(const dlsm_merge_run* batch, int policy, const dlsm_merge_output* out,
+                              MemtableSortPlan& P) {
+  CompactionMergePlan one;
+  DLSM_CHECK(compaction_merge_plan(batch, 1, policy, out, one));
+  DLSM_CHECK(plan_memtable_sort(batch->keys.n, kSortMaxWgs, P));
+  P.tab.runs[0] = one.tab.runs[0];
+  return DLSM_OK;
+}
+
+int dlsm_memtable_sort_dev(dlsm_ctx* ctx, const dlsm_merge_run* batch, int policy, uint64_t smallest_snapshot,
+                           const dlsm_merge_output* out) {
+  if (!ctx) return DLSM_E_ARG;
+  MemtableSortPlan P;
+  DLSM_CHECK(memtable_sort_plan(batch, policy, out, P));
+  if (!merge_output_aligned(out) || !aligned(batch->keys.offsets, 8) || !aligned(batch->value_off, 8)) return DLSM_E_ARG;
+  if (ctx->fault) return -ctx->fault;
+  return compaction_merge_launch(ctx, P, policy, smallest_snapshot, out, nullptr, nullptr, nullptr, &P);
+}
+
+// The host form: the records under std::stable_sort with the kernels'
+// comparator, then the merge's host decide and pack.
+int dlsm_memtable_sort(dlsm_ctx* ctx, const dlsm_merge_run* batch, int policy, uint64_t smallest_snapshot,
+                       const dlsm_merge_output* out) {
+  MemtableSortPlan P;
+  DLSM_CHECK(memtable_sort_plan(batch, policy, out, P));
+  if (ctx && ctx->fault) return -ctx->fault;
+  const CmRun* runs = P.tab.runs;
+  std::vector<CmRec> buf[2] = {std::vector<CmRec>(P.n), std::vector<CmRec>()};
+  uint64_t flags = 0;
+  for (uint64_t i = 0; i < P.n; i++) {
+    bool sk;
+    buf[0][i] = cm_record(runs[0], 0, i, &sk);
+    if (sk) flags |= kCmShortKey;
+  }
+  if (!flags)
+    std::stable_sort(buf[0].begin(), buf[0].end(),
+                     [runs](const CmRec& x, const CmRec& y) { return cm_rec_cmp(x, y, runs) < 0; });
   return compaction_merge_host<false>(P, buf, flags, policy, smallest_snapshot, out);
 }
 

@@ -9,6 +9,7 @@
 #include "compaction_merge.h"
 #include "index_seek.h"
 #include "kv_read.h"
+#include "memtable_sort.h"
 #include "read_plan.h"
 #include "shard_route.h"
 #include "table_build.h"
@@ -677,5 +678,14 @@ hipError_t launch_table_record(const CmDev& a, const TsDev& t, hipStream_t s);
 // tables, or nullptr: packed runs.
 hipError_t launch_compaction_merge(const CmDev& a, const uint32_t* tiles, hipEvent_t* ev, hipStream_t s,
                                    const TsDev* ts = nullptr);
+// The merge's last three launches alone (decide, offsets, gather; packed runs)
+// over the records in rec[n_passes & 1]; ev: an event behind each, or nullptr.
+hipError_t launch_compaction_merge_tail(const CmDev& a, hipEvent_t* ev, hipStream_t s);
+
+// memtable_sort.hip: one unsorted batch into a sorted run (dlsm_memtable_sort_dev).
+// The same descriptor with n_runs = 1 and n_passes = ms_passes(n), workspace in
+// plan::MemtableSortPlan's layout; the tile sort stands where the record pass
+// stands.  ev: an event around every launch (2 * n_passes + 5), or nullptr.
+hipError_t launch_memtable_sort(const CmDev& a, hipEvent_t* ev, hipStream_t s);
 
 }  // namespace dlsm

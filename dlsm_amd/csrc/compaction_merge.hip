@@ -53,6 +53,7 @@
 #include <hip/hip_runtime.h>
 
 #include "bloom_internal.h"
+#include "merge_pass.h"
 #include "sort_pass.h"
 #include "wg_scan.h"
 
@@ -66,8 +67,6 @@ static_assert(kCmWindow + 1 == kCmBlock, "a thread stages one offset of the wind
 static_assert(kCmSpan % (16 * kCmBlock) == 0, "every lane owns the same number of units of a span");
 static_assert(kCmMaxRuns + 1 <= kCmBlock, "a thread stages one base");
 constexpr int kCmUnits = kCmSpan / (16 * kCmBlock);  // units per lane and span
-
-typedef uint32_t cm_u32x4 __attribute__((ext_vector_type(4)));
 
 struct CmAt {
   const uint64_t* p;
@@ -114,34 +113,6 @@ __device__ __forceinline__ void block_scan3(uint64_t* v, uint64_t (*sh)[kCmWaves
     all[q] = sh[q][kCmWaves];
   }
 }
-
-// The record pass's bits, in every thread (called by the whole workgroup).
-// The first launch behind the record pass -- pass 0's partition, or the decide
-// pass where there is no merge pass -- ORs the workgroups' words (`reduce`) and
-// its workgroup 0 leaves the result in tot[3]; every later launch reads that
-// one word.
-// A table record pass has kCmTableMismatch where the packed one has
-// kCmShortKey.
-template <bool D = false>
-__device__ __forceinline__ uint64_t cm_input_flags(const CmDev& a, bool reduce) {
-  if (!reduce) return a.tot[3];
-  constexpr uint64_t kFirst = D ? kCmTableMismatch : kCmShortKey;
-  int shortk = 0, unsorted = 0;
-  for (uint32_t j = threadIdx.x; j < a.nwg; j += blockDim.x) {
-    const uint64_t f = a.wg_flags[j];
-    shortk |= (f & kFirst) != 0;
-    unsorted |= (f & kCmUnsorted) != 0;
-  }
-  shortk = __syncthreads_or(shortk);
-  unsorted = __syncthreads_or(unsorted);
-  const uint64_t flags = (shortk ? kFirst : 0) | (unsorted ? kCmUnsorted : 0);
-  if (blockIdx.x == 0 && threadIdx.x == 0) a.tot[3] = flags;
-  return flags;
-}
-
-// (a select, not an index: indexing the kernel's argument by a run-time value
-// would put the whole descriptor into scratch)
-__device__ __forceinline__ CmRec* cm_buf(const CmDev& a, uint32_t which) { return which ? a.rec[1] : a.rec[0]; }
 
 __device__ __forceinline__ void cm_store_rec(CmRec* dst, const CmRec& r) {
   cm_u32x4* d = reinterpret_cast<cm_u32x4*>(dst);
@@ -192,49 +163,14 @@ __global__ __launch_bounds__(kCmTileLanes) void cm_partition_kernel(CmDev a, uin
   if (cm_input_flags<D>(a, pass == 0)) return;
   const uint32_t t = blockIdx.x * kCmTileLanes + threadIdx.x;
   if (t >= ntiles) return;
-  const CmPair p = cm_pair_of(a.tab, pass, t);
-  const uint32_t na = p.b0 - p.a0, nb = p.b1 - p.b0;
-  const uint64_t d = static_cast<uint64_t>(t - p.tile0) * kCmTile;
-  const uint32_t diag = d < static_cast<uint64_t>(na) + nb ? static_cast<uint32_t>(d) : na + nb;
-  const CmRec* in = cm_buf(a, pass & 1);
-  a.split[t] = cm_path_split<D>(in + p.a0, na, in + p.b0, nb, diag, a.tab->runs);
+  cm_partition_tile<D>(a, pass, cm_pair_of(a.tab, pass, t), t);
 }
 
 template <bool D>
 __global__ __launch_bounds__(kCmTileLanes) void cm_merge_kernel(CmDev a, uint32_t pass) {
   __shared__ cm_u32x4 s[2 * kCmTile];
   if (cm_input_flags(a, false)) return;
-  const uint32_t t = blockIdx.x;
-  const CmPair p = cm_pair_of(a.tab, pass, t);
-  const uint32_t na_all = p.b0 - p.a0, nb_all = p.b1 - p.b0, len = na_all + nb_all;
-  const uint64_t d64 = static_cast<uint64_t>(t - p.tile0) * kCmTile;
-  if (d64 >= len) return;
-  const uint32_t d0 = static_cast<uint32_t>(d64);
-  const uint32_t d1 = len - d0 > kCmTile ? d0 + kCmTile : len;
-  const uint32_t a_lo = a.split[t], a_hi = d1 == len ? na_all : a.split[t + 1];
-  // (sorted segments give ascending splits; anything else would index outside the tile)
-  if (a_lo > d0 || a_hi < a_lo || a_hi > na_all || a_hi > d1 || d1 - a_hi > nb_all || d0 - a_lo > d1 - a_hi) return;
-  const uint32_t b_lo = d0 - a_lo, na = a_hi - a_lo, cnt = d1 - d0, nb = cnt - na;
-  const cm_u32x4* in = reinterpret_cast<const cm_u32x4*>(cm_buf(a, pass & 1));
-  cm_u32x4* out = reinterpret_cast<cm_u32x4*>(cm_buf(a, (pass & 1) ^ 1));
-  for (uint32_t u = threadIdx.x; u < 2 * cnt; u += kCmTileLanes) {
-    const uint32_t e = u >> 1;
-    const uint64_t r = e < na ? static_cast<uint64_t>(p.a0) + a_lo + e : static_cast<uint64_t>(p.b0) + b_lo + (e - na);
-    s[u] = in[2 * r + (u & 1)];
-  }
-  __syncthreads();
-  CmRec* sr = reinterpret_cast<CmRec*>(s);
-  CmRec o[kCmLane];
-  const uint32_t o0 = threadIdx.x * kCmLane;
-  const uint32_t c = o0 < cnt ? (cnt - o0 < kCmLane ? cnt - o0 : kCmLane) : 0;
-  if (c) cm_merge_lane<D>(sr, na, sr + na, nb, o0, c, o, a.tab->runs);
-  __syncthreads();
-#pragma unroll
-  for (uint32_t k = 0; k < kCmLane; k++)
-    if (k < c) sr[o0 + k] = o[k];
-  __syncthreads();
-  const uint64_t o64 = 2 * (static_cast<uint64_t>(p.a0) + d0);
-  for (uint32_t u = threadIdx.x; u < 2 * cnt; u += kCmTileLanes) out[o64 + u] = s[u];
+  cm_merge_tile<D>(a, pass, cm_pair_of(a.tab, pass, blockIdx.x), blockIdx.x, s);
 }
 
 // The four u64[n] arrays in the record buffer the last pass did not write.
@@ -424,6 +360,22 @@ __global__ __launch_bounds__(kCmBlock) void cm_gather_kernel(CmDev a) {
   cm_gather_stream(a.wvo, w.vsrc, m, vb < a.values_cap ? vb : a.values_cap, a.values, soff, ssrc);
 }
 
+// Decide, offsets and gather over the records the last pass wrote; ev: an event
+// behind each of the three, or nullptr.
+template <bool D>
+hipError_t cm_launch_tail(const CmDev& a, hipEvent_t* ev, hipStream_t s) {
+  hipError_t e;
+  int marks = 0;
+  auto mark = [&]() { return ev ? hipEventRecord(ev[marks++], s) : hipSuccess; };
+  cm_decide_kernel<D><<<a.nwg, kCmBlock, 0, s>>>(a);
+  if ((e = hipGetLastError()) != hipSuccess || (e = mark()) != hipSuccess) return e;
+  cm_offsets_kernel<D><<<a.nwg, kCmBlock, 0, s>>>(a);
+  if ((e = hipGetLastError()) != hipSuccess || (e = mark()) != hipSuccess) return e;
+  cm_gather_kernel<<<a.copy_wgs, kCmBlock, 0, s>>>(a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  return mark();
+}
+
 template <bool D>
 hipError_t cm_launch(const CmDev& a, const uint32_t* tiles, hipEvent_t* ev, hipStream_t s, const TsDev* ts) {
   hipError_t e;
@@ -444,16 +396,14 @@ hipError_t cm_launch(const CmDev& a, const uint32_t* tiles, hipEvent_t* ev, hipS
     cm_merge_kernel<D><<<nt, kCmTileLanes, 0, s>>>(a, p);
     if ((e = hipGetLastError()) != hipSuccess || (e = mark()) != hipSuccess) return e;
   }
-  cm_decide_kernel<D><<<a.nwg, kCmBlock, 0, s>>>(a);
-  if ((e = hipGetLastError()) != hipSuccess || (e = mark()) != hipSuccess) return e;
-  cm_offsets_kernel<D><<<a.nwg, kCmBlock, 0, s>>>(a);
-  if ((e = hipGetLastError()) != hipSuccess || (e = mark()) != hipSuccess) return e;
-  cm_gather_kernel<<<a.copy_wgs, kCmBlock, 0, s>>>(a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  return mark();
+  return cm_launch_tail<D>(a, ev ? ev + marks : nullptr, s);
 }
 
 }  // namespace
+
+hipError_t launch_compaction_merge_tail(const CmDev& a, hipEvent_t* ev, hipStream_t s) {
+  return cm_launch_tail<false>(a, ev, s);
+}
 
 hipError_t launch_compaction_merge(const CmDev& a, const uint32_t* tiles, hipEvent_t* ev, hipStream_t s,
                                    const TsDev* ts) {

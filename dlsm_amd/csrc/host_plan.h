@@ -1334,5 +1334,32 @@ inline int plan_compaction_tables(const uint32_t* file_n, const uint8_t* held, u
   return DLSM_OK;
 }
 
+// ---- memtable sort (memtable_sort.hip) -----------------------------------------
+// dlsm_memtable_sort_dev from the batch's pair count alone: ms_tiles(n) tiles
+// sorted in LDS, then ms_passes(n) passes whose pairs are ms_pair's arithmetic
+// (memtable_sort.h), so the table's pair lists stay empty and tab.n_passes is 0
+// -- the batch is run 0 of the table, where the comparator's byte path and the
+// gather find it.  The grid of the tile sort, decide and offset passes and the
+// workspace are plan_compaction_merge's over one run (80 bytes per pair plus
+// the table and the partial sums), with the splits of a pass's ms_tiles(n)
+// tiles behind them.  tab.runs[0] is left to the caller.
+struct MemtableSortPlan : CompactionMergePlan {
+  uint32_t tiles = 0, passes = 0;
+};
+
+inline int plan_memtable_sort(uint64_t n, uint32_t max_wgs, MemtableSortPlan& P) {
+  if (n > 0xffffffffull || max_wgs == 0) return DLSM_E_ARG;
+  const int st = plan_compaction_merge(&n, 1, max_wgs, P);  // (resets every field of the base)
+  if (st != DLSM_OK) return st;
+  P.tiles = ms_tiles(n);
+  P.passes = ms_passes(n);
+  P.max_tiles = P.tiles;
+  Layout ws;  // the one-run merge has no pass: its splits make room for the sort's behind the rest
+  ws.at = P.bytes;
+  ws.region(&P.split_off, &P.split_bytes, sizeof(uint32_t) * (static_cast<uint64_t>(P.tiles) + 1));
+  P.bytes = ws.at;
+  return DLSM_OK;
+}
+
 }  // namespace plan
 }  // namespace dlsm

@@ -993,12 +993,53 @@ int dlsm_compaction_merge(dlsm_ctx* ctx, const dlsm_merge_run* runs, int n_runs,
 uint32_t dlsm_merge_tile(void);
 uint32_t dlsm_merge_span(void);
 uint32_t dlsm_merge_chunk(void);
-/* The last dlsm_compaction_merge_dev or dlsm_compaction_merge_tables_dev of
- * the context, once its work has completed: launch_ms[6] (or NULL) gets the device time per launch kind --
+/* The last dlsm_compaction_merge_dev, dlsm_compaction_merge_tables_dev or
+ * dlsm_memtable_sort_dev of the context, once its work has completed:
+ * launch_ms[6] (or NULL) gets the device time per launch kind --
  * record, partition (all passes), merge (all passes), decide, offsets, gather
  * -- from events recorded around the launches; *passes (or NULL) the number
- * of merge passes. */
+ * of merge passes.  For a memtable sort the tile sort's time is in the record
+ * slot and *passes is the number of global passes. */
 int dlsm_compaction_merge_stats(const dlsm_ctx* ctx, double* launch_ms, uint32_t* passes);
+
+/* ---- memtable sort: an unsorted write batch into a flushable run ---------- */
+
+/* The memtable's job at flush time (the skip list of db/memtable.cc keeps
+ * InternalKeyComparator order on the host): n (internal key, value) pairs in
+ * arrival order in, the pairs in the order of InternalKeyComparator::Compare
+ * out, what the policy drops dropped, packed in the table build's input form.
+ * The semantics are dlsm_compaction_merge_dev's with one unsorted batch in the
+ * place of the sorted runs:
+ *   order: as in the merge; two pairs that compare equal (same user key, same
+ *   trailer) leave in ascending input index.  src[j] is the input index of
+ *   output pair j (the run field is 0);
+ *   drop: DLSM_MERGE_KEEP_ALL keeps every pair, DLSM_MERGE_DROP_HIDDEN applies
+ *   rule (A) at sorted positions.  DROP_HIDDEN with smallest_snapshot =
+ *   kMaxSequenceNumber ((1 << 56) - 1) keeps the first entry of each user key
+ *   -- what DLSM_SELECT_FLUSH keeps when every key parses.  A key of type > 1
+ *   is kept and restarts its user key; it is no error;
+ *   merged, key_off, value_off, keys, values, src, the three capacity flags and
+ *   DLSM_MERGE_SHORT_KEY: word for word the merge's.  Totals are exact under
+ *   any cap, nothing is written at or past a cap or a total, and with a short
+ *   key only `merged` (n_in and flags) is written and no key is read further.
+ *   DLSM_MERGE_UNSORTED is never set.
+ * n = 0 is valid; n > UINT32_MAX returns DLSM_E_ARG.  DLSM_OPT_FAULT_INJECT
+ * makes the calls return the injected error.
+ * dlsm_memtable_sort_dev: every pointer inside *batch and *out device memory
+ * (*batch and *out themselves host memory); asynchronous on the context's
+ * stream: 2 * passes + 4 launches whatever the batch holds, passes =
+ * ceil(log2(ceil(n / dlsm_memtable_sort_tile()))) -- a tile sort in LDS, a
+ * partition and a merge per pass, then the merge's decide, offsets and gather;
+ * no host read-back, no counter shared between workgroups, no result that
+ * depends on the order of atomics.  dlsm_compaction_merge_stats reports it.
+ * dlsm_memtable_sort: every pointer host memory; the same comparator and rule
+ * on the host (no device is touched; ctx may be NULL), synchronous. */
+int dlsm_memtable_sort_dev(dlsm_ctx* ctx, const dlsm_merge_run* batch, int policy, uint64_t smallest_snapshot,
+                           const dlsm_merge_output* out);
+int dlsm_memtable_sort(dlsm_ctx* ctx, const dlsm_merge_run* batch, int policy, uint64_t smallest_snapshot,
+                       const dlsm_merge_output* out);
+/* Records one workgroup sorts in LDS (the size around which the tests are built). */
+uint32_t dlsm_memtable_sort_tile(void);
 
 /* The same merge with its inputs read straight out of opened tables: what a
  * compaction's input iterator yields.  A run is what MakeInputIterator
