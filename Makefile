@@ -8,7 +8,7 @@ SRC := dlsm_amd/csrc/bloom_kernels.hip dlsm_amd/csrc/bloom_capi.hip dlsm_amd/csr
        dlsm_amd/csrc/block_ingest.hip dlsm_amd/csrc/read_plan.hip dlsm_amd/csrc/shard_route.hip dlsm_amd/csrc/index_seek.hip dlsm_amd/csrc/kv_read.hip dlsm_amd/csrc/table_build.hip dlsm_amd/csrc/compaction_merge.hip dlsm_amd/csrc/memtable_sort.hip dlsm_amd/csrc/table_scan.hip dlsm_amd/csrc/compaction_output.hip dlsm_amd/csrc/compaction_filters.hip \
        dlsm_amd/csrc/key_select.hip dlsm_amd/csrc/stream_probe.hip \
        dlsm_amd/csrc/multi_device.hip dlsm_amd/csrc/batcher.hip dlsm_amd/csrc/host_hash.hip
-HDR := dlsm_amd/csrc/bloom_math.h dlsm_amd/csrc/bloom_internal.h dlsm_amd/csrc/host_plan.h dlsm_amd/csrc/read_plan.h dlsm_amd/csrc/shard_route.h dlsm_amd/csrc/index_seek.h dlsm_amd/csrc/kv_read.h dlsm_amd/csrc/table_build.h dlsm_amd/csrc/compaction_merge.h dlsm_amd/csrc/merge_pass.h dlsm_amd/csrc/memtable_sort.h dlsm_amd/csrc/table_scan.h dlsm_amd/csrc/compaction_output.h dlsm_amd/csrc/compaction_filters.h dlsm_amd/csrc/sort_pass.h dlsm_amd/csrc/crc32c_dev.h dlsm_amd/csrc/wg_scan.h include/dlsm_bloom.h
+HDR := dlsm_amd/csrc/bloom_math.h dlsm_amd/csrc/bloom_internal.h dlsm_amd/csrc/host_plan.h dlsm_amd/csrc/read_plan.h dlsm_amd/csrc/shard_route.h dlsm_amd/csrc/index_seek.h dlsm_amd/csrc/kv_read.h dlsm_amd/csrc/table_build.h dlsm_amd/csrc/compaction_merge.h dlsm_amd/csrc/merge_pass.h dlsm_amd/csrc/memtable_sort.h dlsm_amd/csrc/table_scan.h dlsm_amd/csrc/range_scan.h dlsm_amd/csrc/compaction_output.h dlsm_amd/csrc/compaction_filters.h dlsm_amd/csrc/sort_pass.h dlsm_amd/csrc/crc32c_dev.h dlsm_amd/csrc/wg_scan.h include/dlsm_bloom.h
 LIB := dlsm_amd/lib/libdlsm_bloom.so
 OBJ := $(patsubst dlsm_amd/csrc/%.hip,build/%.o,$(SRC))
 

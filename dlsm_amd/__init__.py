@@ -36,7 +36,8 @@ __all__ = [
     "TableData", "kv_read_chunk", "kv_read_span", "kv_pair_read",
     "table_build", "table_build_chunk", "table_build_span", "table_build_bound",
     "compaction_merge", "merge_tile", "merge_span", "merge_chunk", "MERGE_KEEP_ALL", "MERGE_DROP_HIDDEN",
-    "compaction_merge_tables", "MERGE_TABLE_MISMATCH", "memtable_sort", "sort_tile",
+    "compaction_merge_tables", "MERGE_TABLE_MISMATCH", "range_scan", "SCAN_MAX_LIMIT", "SCAN_KEYS_CAP",
+    "SCAN_VALUES_CAP", "SCAN_PAIR_CAP", "SCAN_BAD_TYPE", "SCAN_TABLE_MISMATCH", "memtable_sort", "sort_tile",
     "compaction_output", "compaction_output_bound", "output_tables", "OUTPUT_FILE_FIELDS", "OUTPUT_MAX_FILES", "OUTPUT_FILE_CAP", "OUTPUT_INPUT_FLAGGED",
     "compaction_filters", "compaction_filters_bound", "filter_blocks", "FILTER_REC_FIELDS", "FILTERS_MAX_SLICES", "FILTERS_CAP",
     "FILTERS_TOO_MANY_LINES", "FILTERS_INPUT_FLAGGED",
@@ -244,18 +245,13 @@ def _table_runs(runs):
     return tr, keep
 
 
-def compaction_merge_tables(blocks, files, runs, policy: int = MERGE_DROP_HIDDEN, smallest_snapshot: int = 0, *,
-                            keys_cap: int, values_cap: int, pair_cap: int, ctx: Optional["Context"] = None):
-    """The host form of the merge out of tables (dlsm_compaction_merge_tables;
-    no device is touched): ``blocks[f]`` is file f's sealed index block (bytes)
-    or None, ``files[f]`` the list of its data chunks (bytes) as for TableIndex
-    and TableData, ``runs`` a list of file-number lists -- a level-0 file each,
-    or a deeper level's files in key order.  The caps size the outputs.
-    Returns what compaction_merge returns, src counting through each run's
-    concatenated files."""
+def _host_tables(blocks, files, what):
+    """Sealed index blocks (bytes or None) and chunk lists in the host forms'
+    argument form: (n, block pointers, lengths, chunk records, chunk_begin,
+    what they point into)."""
     n = len(blocks)
     if len(files) != n:
-        raise ValueError("compaction_merge_tables: one chunk list per block")
+        raise ValueError(what + ": one chunk list per block")
     bk = [None if b is None else np.frombuffer(bytes(b) + b"\0", dtype=np.uint8) for b in blocks]
     pa = (C.c_void_p * max(n, 1))(*[None if a is None else a.ctypes.data for a in bk])
     la = (C.c_uint64 * max(n, 1))(*[0 if a is None else a.size - 1 for a in bk])
@@ -267,6 +263,19 @@ def compaction_merge_tables(blocks, files, runs, policy: int = MERGE_DROP_HIDDEN
             recs.append(_L.dlsm_data_chunk(ck[-1].ctypes.data, ck[-1].size - 1))
         begin[f + 1] = len(recs)
     ca = (_L.dlsm_data_chunk * max(len(recs), 1))(*recs)
+    return n, pa, la, ca, begin, (bk, ck)
+
+
+def compaction_merge_tables(blocks, files, runs, policy: int = MERGE_DROP_HIDDEN, smallest_snapshot: int = 0, *,
+                            keys_cap: int, values_cap: int, pair_cap: int, ctx: Optional["Context"] = None):
+    """The host form of the merge out of tables (dlsm_compaction_merge_tables;
+    no device is touched): ``blocks[f]`` is file f's sealed index block (bytes)
+    or None, ``files[f]`` the list of its data chunks (bytes) as for TableIndex
+    and TableData, ``runs`` a list of file-number lists -- a level-0 file each,
+    or a deeper level's files in key order.  The caps size the outputs.
+    Returns what compaction_merge returns, src counting through each run's
+    concatenated files."""
+    n, pa, la, ca, begin, _held = _host_tables(blocks, files, "compaction_merge_tables")
     tr, _keep = _table_runs(runs)
     keys, values = np.zeros(max(keys_cap, 1), dtype=np.uint8), np.zeros(max(values_cap, 1), dtype=np.uint8)
     key_off, value_off = np.zeros(pair_cap + 1, dtype=np.uint64), np.zeros(pair_cap + 1, dtype=np.uint64)
@@ -278,6 +287,49 @@ def compaction_merge_tables(blocks, files, runs, policy: int = MERGE_DROP_HIDDEN
     m = tuple(int(x) for x in merged)
     p = min(m[1], pair_cap)
     return (keys[:min(m[2], keys_cap)], key_off[:p + 1], values[:min(m[3], values_cap)], value_off[:p + 1], src[:p], m)
+
+
+SCAN_MAX_LIMIT = 1024  # DLSM_SCAN_MAX_LIMIT
+SCAN_KEYS_CAP, SCAN_VALUES_CAP, SCAN_PAIR_CAP, SCAN_BAD_TYPE, SCAN_TABLE_MISMATCH = 1, 2, 4, 8, 32
+
+
+def _scan_out(q, limit, count, pair_begin, handle, keys, keys_cap, key_off, values, values_cap, value_off, pair_cap,
+              scanned):
+    for x, nb, what in ((count, 4 * q, "count"), (pair_begin, 8 * (q + 1), "pair_begin"), (handle, 16 * q * limit, "handle"),
+                        (keys, keys_cap, "keys"), (values, values_cap, "values"), (key_off, 8 * (pair_cap + 1), "key_off"),
+                        (value_off, 8 * (pair_cap + 1), "value_off"), (scanned, 40, "scanned")):
+        _need(x, nb, what)
+    return _L.dlsm_scan_output(_ptr(count), _ptr(pair_begin), _ptr(handle), _ptr(keys), keys_cap, _ptr(key_off),
+                               _ptr(values), values_cap, _ptr(value_off), pair_cap, _ptr(scanned))
+
+
+def range_scan(blocks, files, runs, starts: "Keys", snapshot: int, limit: int, *, keys_cap: int, values_cap: int,
+               pair_cap: int, ctx: Optional["Context"] = None):
+    """The host form of the range scan (dlsm_range_scan; no device is touched):
+    tables and ``runs`` as for compaction_merge_tables, ``starts`` the scans'
+    start user keys (host arrays).  Scan q is Seek(starts[q]) and Next() until
+    ``limit`` pairs are yielded under ``snapshot``.  The caps size the outputs.
+    Returns a dict: count uint32[Q], pair_begin uint64[Q + 1], handle
+    uint64[Q * limit, 2] (offset, size | file << 32), keys, key_off, values,
+    value_off (cut at min(total, cap)) and scanned = (n_scans, n_pairs,
+    key_bytes, value_bytes, flags)."""
+    n, pa, la, ca, begin, _held = _host_tables(blocks, files, "range_scan")
+    tr, _keep = _table_runs(runs)
+    q = starts.n
+    o = dict(count=np.zeros(q, dtype=np.uint32), pair_begin=np.zeros(q + 1, dtype=np.uint64),
+             handle=np.zeros((q * limit, 2), dtype=np.uint64), keys=np.zeros(max(keys_cap, 1), dtype=np.uint8),
+             key_off=np.zeros(pair_cap + 1, dtype=np.uint64), values=np.zeros(max(values_cap, 1), dtype=np.uint8),
+             value_off=np.zeros(pair_cap + 1, dtype=np.uint64), scanned=np.zeros(5, dtype=np.uint64))
+    so = _scan_out(q, limit, o["count"], o["pair_begin"], o["handle"], o["keys"], keys_cap, o["key_off"], o["values"],
+                   values_cap, o["value_off"], pair_cap, o["scanned"])
+    ks = starts.c()
+    check(lib().dlsm_range_scan(ctx.h if ctx is not None else None, pa, la, ca, begin.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                n, tr, len(runs), C.byref(ks), snapshot, limit, C.byref(so)), "range_scan")
+    m = tuple(int(x) for x in o["scanned"])
+    p = min(m[1], pair_cap)
+    o.update(keys=o["keys"][:min(m[2], keys_cap)], values=o["values"][:min(m[3], values_cap)], key_off=o["key_off"][:p + 1],
+             value_off=o["value_off"][:p + 1], scanned=m)
+    return o
 
 
 def compaction_merge(runs, policy: int = MERGE_DROP_HIDDEN, smallest_snapshot: int = 0, *,
@@ -1445,6 +1497,10 @@ class Context:
                                 **kw):
         """The host-memory form (see dlsm_amd.compaction_merge_tables)."""
         return compaction_merge_tables(blocks, files, runs, policy, smallest_snapshot, ctx=self, **kw)
+
+    def range_scan(self, blocks, files, runs, starts: Keys, snapshot: int, limit: int, **kw):
+        """The host-memory form (see dlsm_amd.range_scan)."""
+        return range_scan(blocks, files, runs, starts, snapshot, limit, ctx=self, **kw)
 
     def compaction_merge_stats(self):
         """(record, partition, merge, decide, offsets, gather) device

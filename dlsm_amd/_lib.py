@@ -106,6 +106,12 @@ class dlsm_merge_output(C.Structure):
                 ("merged", C.c_void_p)]
 
 
+class dlsm_scan_output(C.Structure):
+    _fields_ = [("count", C.c_void_p), ("pair_begin", C.c_void_p), ("handle", C.c_void_p), ("keys", C.c_void_p),
+                ("keys_cap", C.c_uint64), ("key_off", C.c_void_p), ("values", C.c_void_p), ("values_cap", C.c_uint64),
+                ("value_off", C.c_void_p), ("pair_cap", C.c_uint64), ("scanned", C.c_void_p)]
+
+
 class DlsmError(RuntimeError):
     def __init__(self, status: int, what: str = ""):
         self.status = status
@@ -261,6 +267,9 @@ SIGNATURES = [
     ("dlsm_compaction_merge_tables", C.c_int, [_VP, C.POINTER(_VP), _U64P, C.POINTER(dlsm_data_chunk),
                                                C.POINTER(C.c_uint32), C.c_int, C.POINTER(dlsm_table_run), C.c_int, C.c_int,
                                                C.c_uint64, C.POINTER(dlsm_merge_output)]),
+    ("dlsm_range_scan", C.c_int, [_VP, C.POINTER(_VP), _U64P, C.POINTER(dlsm_data_chunk), C.POINTER(C.c_uint32), C.c_int,
+                                  C.POINTER(dlsm_table_run), C.c_int, C.POINTER(dlsm_keyset), C.c_uint64, C.c_uint32,
+                                  C.POINTER(dlsm_scan_output)]),
     ("dlsm_memtable_sort_dev", C.c_int, [_VP, C.POINTER(dlsm_merge_run), C.c_int, C.c_uint64,
                                          C.POINTER(dlsm_merge_output)]),
     ("dlsm_memtable_sort", C.c_int, [_VP, C.POINTER(dlsm_merge_run), C.c_int, C.c_uint64,

@@ -80,6 +80,35 @@ def merge_runs(runs, policy=DROP_HIDDEN, snapshot=0):
     return pairs, src
 
 
+def scan_runs(runs, start: bytes, snapshot: int, limit: int):
+    """``DBIter`` (db/db_iter.cc:141-212, 283-298) over the merged runs after
+    ``Seek(start)``, for ``limit`` calls of ``key()`` / ``Next()``: runs as for
+    merge_runs, merged in its order.  Returns (pairs, src, bad_type): the
+    yielded (internal key, value) list, run << 32 | index in run of each, and
+    whether the iterator passed an entry whose type byte does not parse."""
+    items = sorted(((ik[:-8], -trailer(ik), r, i) for r, run in enumerate(runs) for i, (ik, _) in enumerate(run)))
+    pairs, src, bad_type = [], [], False
+    skipping, skip = False, None  # FindNextUserEntry's state: entries of user key `skip` are hidden
+    for user, neg, r, i in items:
+        if len(pairs) == limit:
+            break
+        if (user, neg) < (start, -(snapshot << 8 | 1)):  # before where Seek(start || snapshot, kTypeForSeek) lands
+            continue
+        t = -neg
+        if (t & 0xff) > 1:  # ParseKey fails: the entry is passed over
+            bad_type = True
+            continue
+        if (t >> 8) > snapshot:
+            continue
+        if skipping and user == skip:
+            continue
+        skipping, skip = True, user  # a deletion hides the key's older entries; so does a yielded value, by Next()
+        if (t & 0xff) == 1:
+            pairs.append(runs[r][i])
+            src.append(r << 32 | i)
+    return pairs, src, bad_type
+
+
 def open_output(ctx, data, index, chunk_end, files):
     """Open what ``Context.compaction_output_dev`` wrote where it lies: ``data``
     and ``index`` are the call's device tensors, ``chunk_end`` and ``files``

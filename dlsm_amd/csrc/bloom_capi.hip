@@ -3978,6 +3978,117 @@ int dlsm_compaction_merge_tables(dlsm_ctx* ctx, const uint8_t* const* blocks, co
 }
 
 // ---------------------------------------------------------------------------
+// Range scan: Seek + Next over sealed tables (db/db_iter.cc:141-212, 283-298;
+// range_scan.h)
+// ---------------------------------------------------------------------------
+static_assert(DLSM_SCAN_MAX_LIMIT == kRsMaxLimit && DLSM_SCAN_KEYS_CAP == kRsKeysCap &&
+                  DLSM_SCAN_VALUES_CAP == kRsValuesCap && DLSM_SCAN_PAIR_CAP == kRsPairCap &&
+                  DLSM_SCAN_BAD_TYPE == kRsBadType && DLSM_SCAN_TABLE_MISMATCH == kRsTableMismatch,
+              "scan constants");
+
+// The checks on everything but the tables.
+static int range_scan_args_ok(const dlsm_keyset* starts, uint64_t snapshot, const dlsm_scan_output* out) {
+  if (!starts || !out || snapshot > ((uint64_t(1) << 56) - 1)) return DLSM_E_ARG;
+  DLSM_CHECK(validate_keyset(*starts));
+  if (starts->n && (!out->count || !out->pair_begin || !out->handle || !out->key_off || !out->value_off || !out->scanned))
+    return DLSM_E_ARG;
+  if ((out->keys_cap && !out->keys) || (out->values_cap && !out->values)) return DLSM_E_ARG;
+  return DLSM_OK;
+}
+
+namespace {
+struct RsHostFiles {
+  const TsFile* file;
+  uint32_t entries(uint32_t f) const { return file[f].index.n; }
+  RsFile at(uint32_t f) const { return RsFile{file[f].index, file[f].chunks}; }
+};
+}  // namespace
+
+// The host form: rs_scan_one scan after scan, then the offsets and the copies
+// -- nothing reaches the caller's arrays before every scan's pairs have passed.
+int dlsm_range_scan(dlsm_ctx* ctx, const uint8_t* const* blocks, const uint64_t* lens, const dlsm_data_chunk* chunks,
+                    const uint32_t* chunk_begin, int n_files, const dlsm_table_run* runs, int n_runs,
+                    const dlsm_keyset* starts, uint64_t snapshot, uint32_t limit, const dlsm_scan_output* out) {
+  if (n_files < 0 || (n_files > 0 && (!blocks || !lens))) return DLSM_E_ARG;
+  DLSM_CHECK(range_scan_args_ok(starts, snapshot, out));
+  TableDataPlan data;
+  DLSM_CHECK(plan_tabledata(chunks, chunk_begin, n_files, data));
+  const uint32_t nf = static_cast<uint32_t>(n_files);
+  std::vector<TsFile> file(nf);
+  std::vector<uint32_t> file_n(nf, 0);
+  std::vector<uint8_t> held(nf, 0);
+  std::vector<const uint8_t*> base(data.end.size());
+  for (size_t c = 0; c < base.size(); c++) base[c] = chunks[c].base;
+  for (uint32_t f = 0; f < nf; f++) {
+    const uint32_t c0 = chunk_begin[f], c1 = chunk_begin[f + 1];
+    file[f].chunks = KvChunks{data.end.data() + c0, base.data() + c0, c1 - c0};
+    if (blocks[f] && lens[f] >= 5) (void)index_header_valid(blocks[f], lens[f] - 5, &file[f].index);
+    else file[f].index = IndexView{nullptr, 0, 0};
+    file_n[f] = file[f].index.n;
+    held[f] = blocks[f] && (file_n[f] == 0 || c1 > c0);
+  }
+  RangeScanPlan P;
+  DLSM_CHECK(plan_range_scan(file_n.data(), held.data(), nf, runs, n_runs, starts->n, limit, P));
+  if (ctx && ctx->fault) return -ctx->fault;
+  if (P.q == 0) return DLSM_OK;
+  const RsRuns& R = P.runs;
+  for (uint32_t k = 0; k < R.first[R.n_runs]; k++)
+    if (!index_block_open_host(blocks[R.file[k]], lens[R.file[k]], &file[R.file[k]].index)) return DLSM_E_CORRUPT;
+  const RsHostFiles files{file.data()};
+  std::vector<KvHandle> handle(P.slots, KvHandle{0, 0, 0});
+  std::vector<CmDesc> desc(P.slots);
+  std::vector<uint32_t> count(P.q);
+  uint64_t flags = 0;
+  for (uint64_t q = 0; q < P.q; q++) {
+    const uint64_t s = starts->offsets ? starts->offsets[q] : q * starts->key_len;
+    uint64_t l = starts->offsets ? starts->offsets[q + 1] - s : starts->key_len;
+    l = l > starts->suffix_len ? l - starts->suffix_len : 0;  // ExtractUserKey
+    const RsResult r = rs_scan_one(files, R, starts->bytes + s, static_cast<uint32_t>(l), snapshot, limit,
+                                   handle.data() + q * limit, desc.data() + q * limit);
+    count[q] = r.count;
+    flags |= r.flags;
+  }
+  if (flags & kRsTableMismatch) {
+    out->scanned[0] = P.q;
+    out->scanned[1] = out->scanned[2] = out->scanned[3] = 0;
+    out->scanned[4] = flags;
+    return DLSM_OK;
+  }
+  uint64_t p = 0, ko = 0, vo = 0;
+  for (uint64_t q = 0; q < P.q; q++) {
+    out->count[q] = count[q];
+    out->pair_begin[q] = p;
+    for (uint32_t j = 0; j < limit; j++) {
+      const KvHandle& h = handle[q * limit + j];
+      out->handle[q * limit + j] = j < count[q] ? dlsm_kv_handle{h.offset, h.size, h.file} : dlsm_kv_handle{0, 0, 0};
+    }
+    for (uint32_t j = 0; j < count[q]; j++, p++) {
+      const CmDesc& d = desc[q * limit + j];
+      if (p <= out->pair_cap) {
+        out->key_off[p] = ko;
+        out->value_off[p] = vo;
+      }
+      const uint8_t* src = reinterpret_cast<const uint8_t*>(d.addr) + 8;
+      if (ko < out->keys_cap) memcpy(out->keys + ko, src, std::min<uint64_t>(d.key_size, out->keys_cap - ko));
+      if (d.value_size && vo < out->values_cap)
+        memcpy(out->values + vo, src + d.key_size, std::min<uint64_t>(d.value_size, out->values_cap - vo));
+      ko += d.key_size;
+      vo += d.value_size;
+    }
+  }
+  out->pair_begin[P.q] = p;
+  if (p <= out->pair_cap) {
+    out->key_off[p] = ko;
+    out->value_off[p] = vo;
+  }
+  flags |= (ko > out->keys_cap ? kRsKeysCap : 0) | (vo > out->values_cap ? kRsValuesCap : 0) |
+           (p > out->pair_cap ? kRsPairCap : 0);
+  const uint64_t scanned[5] = {P.q, p, ko, vo, flags};
+  memcpy(out->scanned, scanned, sizeof(scanned));
+  return DLSM_OK;
+}
+
+// ---------------------------------------------------------------------------
 // Legacy FilterPolicy format (util/bloom.cc)
 // ---------------------------------------------------------------------------
 int dlsm_bloom_legacy_build_dev(dlsm_ctx* ctx, const dlsm_build_job* jobs, int n_jobs,

@@ -16,6 +16,7 @@
 #include "compaction_output.h"
 #include "compaction_filters.h"
 #include "table_scan.h"
+#include "range_scan.h"
 
 namespace dlsm {
 

@@ -1361,5 +1361,36 @@ inline int plan_memtable_sort(uint64_t n, uint32_t max_wgs, MemtableSortPlan& P)
   return DLSM_OK;
 }
 
+// ---- range scan (range_scan.h) --------------------------------------------------
+// dlsm_range_scan from the files' entry counts, the runs' file lists, the scan
+// count and the limit alone: plan_compaction_tables' argument rules over the
+// runs, and the runs' listed files (RsRuns).
+struct RangeScanPlan {
+  RsRuns runs;
+  uint64_t q = 0, slots = 0;  // scans; q * limit handle slots
+};
+
+inline int plan_range_scan(const uint32_t* file_n, const uint8_t* held, uint32_t n_files, const dlsm_table_run* runs,
+                           int n_runs, uint64_t q, uint32_t limit, RangeScanPlan& P) {
+  if (limit < 1 || limit > kRsMaxLimit) return DLSM_E_ARG;
+  {
+    CompactionTablesPlan T;  // (the rules, and the files in listed order)
+    const int st = plan_compaction_tables(file_n, held, n_files, runs, n_runs, kSortMaxWgs, T);
+    if (st != DLSM_OK) return st;
+    P.runs = RsRuns();
+    P.runs.n_runs = static_cast<uint32_t>(n_runs);
+    uint32_t k = 0;
+    for (int r = 0; r < n_runs; r++) {
+      P.runs.first[r] = k;
+      for (uint32_t j = 0; j < runs[r].n_files; j++, k++) P.runs.file[k] = T.ts.file[k];
+    }
+    for (uint32_t r = static_cast<uint32_t>(n_runs); r <= kCmMaxRuns; r++) P.runs.first[r] = k;
+  }
+  if (q * limit > 0xffffffffull) return DLSM_E_ARG;
+  P.q = q;
+  P.slots = q * limit;
+  return DLSM_OK;
+}
+
 }  // namespace plan
 }  // namespace dlsm

@@ -1097,6 +1097,82 @@ int dlsm_compaction_merge_tables(dlsm_ctx* ctx, const uint8_t* const* blocks, co
                                  const dlsm_table_run* runs, int n_runs, int policy,
                                  uint64_t smallest_snapshot, const dlsm_merge_output* out);
 
+/* ---- range scan: Seek + Next over opened tables --------------------------- */
+
+/* What DB::NewIterator, Seek(start) and a row of Next() calls yield
+ * (DBIter, db/db_iter.cc:141-212, 283-298, over a MergingIterator,
+ * table/merger.cc) for a batch of Q scans over the same runs; the runs are
+ * dlsm_compaction_merge_tables' (one level-0 file, or a deeper level's
+ * files in key order), under the same DLSM_E_ARG rules.  Scan q:
+ *   the runs are merged in InternalKeyComparator order, equal internal keys to
+ *   the lower run; the walk starts at the first entry >= starts[q] ||
+ *   Fixed64(snapshot << 8 | 1) (starts: user keys, or internal keys with
+ *   suffix_len = 8 of which ExtractUserKey is used);
+ *   an entry whose sequence is above snapshot is passed over; an entry whose
+ *   type byte is above 1 is passed over and sets DLSM_SCAN_BAD_TYPE (ParseKey
+ *   fails) -- only entries the iterator reaches count: none behind the pair
+ *   that fills the limit;
+ *   the first remaining entry of a user key decides the key: type 1 yields the
+ *   pair, type 0 nothing; every later entry of that user key is hidden;
+ *   the scan stops after `limit` yielded pairs (1..DLSM_SCAN_MAX_LIMIT) or when
+ *   every run is exhausted.
+ * Outputs, each a pure function of the inputs:
+ *   count[q]: the pairs scan q yielded; pair_begin[q], q <= Q: the exclusive
+ *   sum of count;
+ *   handle[q * limit + j]: the j-th yielded pair of scan q -- file in the
+ *   tableindex numbering, offset and size from the index entry; the slots from
+ *   count[q] on are zero;
+ *   key_off / keys / value_off / values: the yielded pairs packed in the order
+ *   (q, j), pair p = pair_begin[q] + j, under dlsm_compaction_merge_dev's cap
+ *   rules: offsets written for p <= min(n_pairs, pair_cap) and exact whatever
+ *   the caps are, every byte below min(total, cap) the right one, nothing
+ *   written at or past a cap or past a total.  keys holds the pairs' internal
+ *   keys as stored -- a dlsm_keyset with suffix_len = 8 over them is
+ *   DBIter::key() -- values the value bytes;
+ *   scanned: {n_scans, n_pairs, key_bytes, value_bytes, flags}.
+ * DLSM_SCAN_TABLE_MISMATCH: a yielded entry fails the rules
+ * dlsm_compaction_merge_tables applies to one entry (the handle names no
+ * `size` bytes of one chunk, the pair's header or key bytes disagree with the
+ * entry, the offset is not its predecessor's offset + size).  Then only
+ * `scanned` is written, and of it only n_scans and flags are specified.
+ * Overlapping files of one level are the caller's breach (Version rules them
+ * out): the result is unspecified.  No byte outside the index contents and the
+ * chunks is ever read, flag or not.
+ * DLSM_E_ARG besides the runs' rules: limit outside 1..DLSM_SCAN_MAX_LIMIT,
+ * snapshot above kMaxSequenceNumber, Q * limit above UINT32_MAX, a missing
+ * output (keys / values may be NULL with a cap of 0).  Q = 0 returns DLSM_OK
+ * and touches nothing.  DLSM_OPT_FAULT_INJECT makes the calls return the
+ * injected error.
+ * dlsm_range_scan: the sealed index blocks and chunks in host memory, in the
+ * arguments' form of dlsm_compaction_merge_tables, starts and *out's arrays
+ * host memory; the rules run on the host one scan after the other (no device
+ * is touched; ctx may be NULL), synchronous.  There is no device form yet
+ * (DESIGN section 9, item 24).  A listed block that would not open returns DLSM_E_CORRUPT. */
+#define DLSM_SCAN_MAX_LIMIT 1024u
+#define DLSM_SCAN_KEYS_CAP 1u
+#define DLSM_SCAN_VALUES_CAP 2u
+#define DLSM_SCAN_PAIR_CAP 4u
+#define DLSM_SCAN_BAD_TYPE 8u
+#define DLSM_SCAN_TABLE_MISMATCH 32u
+
+typedef struct {
+  uint32_t* count;        /* u32[Q] */
+  uint64_t* pair_begin;   /* u64[Q + 1] */
+  dlsm_kv_handle* handle; /* [Q * limit] */
+  uint8_t* keys;          /* packed internal keys */
+  uint64_t keys_cap;
+  uint64_t* key_off;      /* u64[pair_cap + 1] */
+  uint8_t* values;        /* packed values */
+  uint64_t values_cap;
+  uint64_t* value_off;    /* u64[pair_cap + 1] */
+  uint64_t pair_cap;
+  uint64_t* scanned;      /* u64[5]: n_scans, n_pairs, key_bytes, value_bytes, flags */
+} dlsm_scan_output;
+
+int dlsm_range_scan(dlsm_ctx* ctx, const uint8_t* const* blocks, const uint64_t* lens,
+                    const dlsm_data_chunk* chunks, const uint32_t* chunk_begin, int n_files,
+                    const dlsm_table_run* runs, int n_runs, const dlsm_keyset* starts, uint64_t snapshot,
+                    uint32_t limit, const dlsm_scan_output* out);
 /* ---- compaction output: a merged run cut into size-capped tables --------- */
 
 /* The last step of a compaction: DBImpl::DoCompactionWork closes its output
